@@ -27,7 +27,13 @@ Rank 0 prints ONE JSON line (contract in the task statement), including
                  PROCESSED (the cull leaves blocks out: pf_profile_read_run) / HIP-event time on the map's stream; `frac_full_canvas` = the same
                  with the bytes of every canvas tile (what rounds 1-4 printed as `frac`); `traffic` / `frac_delivered` = HBM bytes from the PMC
                  passes of exactly this window (profiles/pmc_traffic.json, tools/profile_windows.sh), null for a window without a pass
-  cpu_baseline : the oracle (CPU port of MultiBandMap2DCPU) timed on a bounded sample.
+  cpu_baseline : the oracle (CPU port of MultiBandMap2DCPU) timed on a bounded sample (--full only).
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the benchmark measures -- the copy
+ceiling, the other pyramid type, the runs without cull / lookahead, the CPU baselines, the host-, jpeg- and output-side
+rates, the single-band path and, with N > 1, the tile-sharded probe -- runs only with --full (--no-cpu then leaves out
+the CPU / host-feed / second-dtype legs, as before).
+--dump-outputs DIR writes, after the timed steps, what the timed path computed: rank 0's map as a caller reads it back
+(pf_get_tile_level), for a seeded sample of the tiles of the last timed keyframe's canvas, as float32 .npy files.
 Every leg after the timed GPU region is guarded: a failure there becomes {"error": ...} inside
 the line and never loses the GPU measurement.
 """
@@ -383,6 +389,44 @@ def canvas_shares(m):
     return {"rendered_share_rank0": round(1.0 - (ct * 16 + cc) * 4096.0 / canvas, 4), "level0_run_share_rank0": round(rs["level0_px"] / canvas, 4)}
 
 
+DUMP_TILES = 32           # tiles sampled into --dump-outputs: every level's Laplacian + weight, ~1.4 MB a tile in float32
+
+
+def dump_outputs(pf, wl, m, last_pose, out_dir, max_tiles=DUMP_TILES, seed=0):
+    """--dump-outputs: the map the timed steps left, as a caller reads it back (Ele::pyr_laplace / Ele::weights through
+    pf_get_tile_level).  Tiles: a seeded sample of those of the last timed keyframe's canvas (all tiles of the map if its canvas
+    holds none), every level, float32.  Files: tiles.npy (stable coordinates of every tile of the map), sample_tiles.npy (the
+    sampled ones, in the order of the stacks), lap_L<l>.npy (n x s x s x 3) and weight_L<l>.npy (n x s x s)."""
+    os.makedirs(out_dir, exist_ok=True)
+    have = sorted(m.tiles())
+    dims, geo = m.grid()
+    cand = []
+    pts = pf.footprint(CAM, pf.se3_mul(pf.se3_inverse(wl.IDENTITY_PLANE), last_pose))
+    if pts is not None:
+        inv = 1.0 / geo[4]
+        x0 = int(np.floor((pts[:, 0].min() - geo[0]) * inv)) + dims[2]; x1 = int(np.ceil((pts[:, 0].max() - geo[0]) * inv)) + dims[2]
+        y0 = int(np.floor((pts[:, 1].min() - geo[1]) * inv)) + dims[3]; y1 = int(np.ceil((pts[:, 1].max() - geo[1]) * inv)) + dims[3]
+        cand = [t for t in have if x0 <= t[0] < x1 and y0 <= t[1] < y1]
+    if not cand:
+        cand = have
+    sel = []
+    for i in np.random.default_rng(seed).permutation(len(cand)):
+        if len(sel) == max_tiles:
+            break
+        if m.tile_level(*cand[i], 0) is not None:          # a tile the store holds without a pyramid has nothing to read back
+            sel.append(cand[i])
+    np.save(os.path.join(out_dir, "tiles.npy"), np.array(have, np.float64).reshape(-1, 2))
+    np.save(os.path.join(out_dir, "sample_tiles.npy"), np.array(sel, np.float64).reshape(-1, 2))
+    for lv in range(m.num_levels):
+        laps, ws = [], []
+        for t in sel:
+            lap, w = m.tile_level(*t, lv)
+            laps.append(lap.astype(np.float32)); ws.append(w.astype(np.float32))
+        s = pf.ELE_PIXELS >> lv
+        np.save(os.path.join(out_dir, "lap_L%d.npy" % lv), np.stack(laps) if laps else np.zeros((0, s, s, 3), np.float32))
+        np.save(os.path.join(out_dir, "weight_L%d.npy" % lv), np.stack(ws) if ws else np.zeros((0, s, s), np.float32))
+
+
 def timed_run(m, run, W, K, event_every, barrier):
     """W untimed steps with every kernel timed (finds the dominant kernel), then K timed steps with HIP events
     around every n-th launch of that kernel only.  Returns (seconds, dominant kernel, its record, warm-up records)."""
@@ -471,7 +515,7 @@ def main():
     ap.add_argument("--int16", action="store_true", help="headline on the reference-default pyramids (CV_16SC3) instead of ForceFloat")
     ap.add_argument("--scale", type=float, default=1.0, help="Map2D.Scale (1 = cfg-A, 0.5 = shipped Default.cfg)")
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic frames kept in HBM")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU / host-feed / second-dtype legs (profiling runs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU / host-feed / second-dtype legs (a plain run has none of them)")
     ap.add_argument("--fused", type=int, default=None, help="pf_options.fused (default: the library's default)")
     ap.add_argument("--event-every", type=int, default=None,
                     help="HIP events around every n-th launch of the dominant kernel in the timed region "
@@ -487,6 +531,11 @@ def main():
                     help="do not fly the 20 - W keyframes of the sortie's first line before the warm-up: a short run then times that "
                          "first line (every tile new, nothing culled), as round 2's driver record did")
     ap.add_argument("--pre", type=int, default=None, help="keyframes of the sortie flown before the warm-up (default 20 - W: its first line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: copy ceiling, other dtype, no-cull / no-lookahead runs, CPU baselines, "
+                         "host / jpeg / output-side rates, single-band path, and with N > 1 the tile-sharded probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (sampled tiles of rank 0's map, float32) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.no_cull:
         os.environ["PF_CULL"] = "0"          # read when a map is created
@@ -670,6 +719,8 @@ def main():
         if N == 1 and isinstance(r, dict) and r.get("alg_bytes_run_per_launch") and dt > 0:
             a = r["alg_bytes_run_per_launch"] / (dt / K) / 1e9
             out["roofline_per_step"] = {"achieved": round(a, 1), "unit": "GB/s", "frac": round(a / HBM_PEAK_GBS, 4), "us_per_step": round(dt / K * 1e6, 2)}
+        if args.dump_outputs:
+            dump_outputs(pf, wl, m, my_sortie[PRE + W + K - 1], args.dump_outputs)
 
     # strong sharding: what a rank renders beyond its share, and the timed seam exchange
     if strong:
@@ -680,13 +731,13 @@ def main():
 
     # ... and in the default (replicas) run of N > 1: the same sortie sharded by tile, with the library's seam exchange
     abandoned = False
-    if N > 1 and not strong and not args.no_strong_probe:
+    if args.full and N > 1 and not strong and not args.no_strong_probe:
         rec, abandoned = run_with_deadline(lambda: strong_probe(pf, wl, torch, dist, rank, N, dev, frames, base, W, K, args.scale, force_float,
                                                                 extra, os.environ.get("PF_DIST_BACKEND", "nccl")), 150)
         if rank == 0:
             out["strong"] = rec
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # measured HBM ceiling on this box: a 1 GiB device-to-device copy, read + write bytes
         def copy_ceiling():
             a_ = torch.empty(1 << 30, dtype=torch.uint8, device="cuda"); b_ = torch.empty_like(a_)
@@ -702,14 +753,14 @@ def main():
             out["roofline"]["copy_ceiling_GBps"] = cc
 
     # the other pyramid type in the same run (the reference's default is CV_16SC3; north_star's parity bar is on fp32)
-    if not args.no_cpu and N == 1:
+    if args.full and not args.no_cpu and N == 1:
         # the same run with the cull off: every tile of every keyframe's canvas rendered, as the reference does (same mosaic; what the
         # headline gains by leaving out quadrants in which the keyframe cannot win the select).  In a child process of its own: rounds 3-4 saw
         # the third timed run inside one process read 2400-4600 keyframes/s at its usual time per launch -- in round 5 found to be the
         # interpreter's heap collection falling due inside the loop (timed_run now keeps it out); the child process stays: it also gives the
         # leg a map store and a cull state of its own.
         def full_render():
-            cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu", "--no-cull", "--steps", str(K), "--warmup", str(W), "--scale", str(args.scale)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu", "--no-cull", "--steps", str(K), "--warmup", str(W), "--scale", str(args.scale)]
             if args.int16:
                 cmd.append("--int16")
             if args.no_pre:
@@ -719,7 +770,7 @@ def main():
             return {"value": j["value"], "unit": "keyframes/s", "dtype": j["dtype"], "ms_per_step": j["ms_per_step"],
                     "culled_tiles": j["config"]["culled_tiles_rank0"], "roofline": j["roofline"]}
         def no_lookahead():
-            cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu", "--lookahead", "0", "--steps", str(K), "--warmup", str(W), "--scale", str(args.scale)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu", "--lookahead", "0", "--steps", str(K), "--warmup", str(W), "--scale", str(args.scale)]
             if args.int16:
                 cmd.append("--int16")
             if args.no_pre:
@@ -747,7 +798,7 @@ def main():
             out["no_lookahead"] = guarded(no_lookahead)
 
 
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         hostf = guarded(lambda: [f.cpu().numpy() for f in frames[:2]])
         if isinstance(hostf, dict):
             out["cpu_baseline"] = hostf

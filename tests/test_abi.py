@@ -19,6 +19,9 @@ def declared_symbols():
 
 
 def test_library_exports_every_declared_symbol(pf):
+    # through lib() first (torch, then the library): a bare dlopen here would load ROCm's HIP runtime and torch later its own copy,
+    # and the GPU tests that follow in the same process would find no device
+    pf.lib()
     lib = ctypes.CDLL(pf.LIB_PATH)
     names = declared_symbols()
     assert len(names) >= 35

@@ -151,3 +151,39 @@ def test_output_side_record_fields(monkeypatch):
     assert abs(r["kernel_alg_GBps"] - 3000.0) < 1 and abs(r["frac"] - 3000.0 / bench.HBM_PEAK_GBS) < 1e-3
     assert r["kernel_tiles_per_s"] == 2000000 and r["tiles_per_s"] > 0 and r["d2h_GBps"] > 0
     assert r["save"]["kernel"] == "save_fused" and r["save"]["mosaic"] == [1024, 1280] and abs(r["save"]["kernel_alg_GBps"] - 2000.0) < 1
+
+
+def test_dump_outputs_files(pf, tmp_path):
+    """bench.dump_outputs against a stand-in map on the bench's own geometry: float32 / float64 files only, well under 64 MB,
+    the sampled tiles inside the last keyframe's canvas and holding a pyramid, the same sample from run to run."""
+    wl = importlib.import_module("pi_slam_fusion_amd.workloads")
+    pose = wl.serpentine(bench.CAM, bench.HEIGHT, 25)[-1]
+
+    class FakeMap:
+        num_levels = 5
+        def grid(self): return [120, 120, 7, 3], [-600.0, -600.0, 600.0, 600.0, 10.0, 256.0]
+        def tiles(self): return [(x, y) for y in range(3, 123) for x in range(7, 127)]
+        def tile_level(self, ix, iy, lv):
+            if (ix + iy) % 7 == 0:
+                return None                          # held without a pyramid
+            s = 256 >> lv
+            return np.full((s, s, 3), ix - iy, np.int16), np.full((s, s), 0.5 * lv, np.float32)
+
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(pf, wl, FakeMap(), pose, a)
+    bench.dump_outputs(pf, wl, FakeMap(), pose, b)
+    names = sorted(os.listdir(a))
+    assert names == sorted(["tiles.npy", "sample_tiles.npy"] + ["lap_L%d.npy" % l for l in range(5)] + ["weight_L%d.npy" % l for l in range(5)])
+    assert sum(os.path.getsize(os.path.join(a, n)) for n in names) < 64 << 20
+    for n in names:
+        x, y = np.load(os.path.join(a, n)), np.load(os.path.join(b, n))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    sel = np.load(os.path.join(a, "sample_tiles.npy")).astype(int)
+    assert len(sel) == bench.DUMP_TILES and all((ix + iy) % 7 for ix, iy in sel)
+    dims, geo = FakeMap().grid()
+    pts = pf.footprint(bench.CAM, pf.se3_mul(pf.se3_inverse(wl.IDENTITY_PLANE), pose))
+    assert (sel[:, 0] >= np.floor((pts[:, 0].min() - geo[0]) / geo[4]) + dims[2]).all()
+    assert (sel[:, 0] < np.ceil((pts[:, 0].max() - geo[0]) / geo[4]) + dims[2]).all()
+    lap0 = np.load(os.path.join(a, "lap_L0.npy"))
+    assert lap0.shape == (bench.DUMP_TILES, 256, 256, 3) and (lap0[:, 0, 0, 0] == sel[:, 0] - sel[:, 1]).all()
+    assert np.load(os.path.join(a, "weight_L4.npy")).shape == (bench.DUMP_TILES, 16, 16)

@@ -5,8 +5,8 @@ O=gpurun_out/r05; mkdir -p $O
 python -m pytest tests -x -q -m gpu > $O/gpu_tests_last.txt 2>&1 || { tail -40 $O/gpu_tests_last.txt; exit 1; }
 tail -2 $O/gpu_tests_last.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-python bench.py > $O/bench_last.json 2> $O/bench_last.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_last.json 2>/dev/null
+python bench.py --full > $O/bench_last.json 2> $O/bench_last.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_last.json 2>/dev/null
 python bench.py --int16 --no-cpu > $O/bench_int16_last.json 2>/dev/null
 python - <<'PY'
 import json

@@ -1,10 +1,10 @@
 O=gpurun_out/r05; mkdir -p $O; export TMPDIR=/tmp
 R=$PWD/tools/ab/lib_r04.so
 tools/abn.sh 4 "--steps 20 --warmup 5" "PF_LIB=$R" "PF_X=1" > $O/ab12_driver.txt 2>&1; cat $O/ab12_driver.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_driver.json 2> $O/r05_bench_driver.err; echo "driver rc $?"
-python bench.py > $O/r05_bench_default.json 2> $O/r05_bench_default.err; echo "default rc $?"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_driver.json 2> $O/r05_bench_driver.err; echo "driver rc $?"
+python bench.py --full > $O/r05_bench_default.json 2> $O/r05_bench_default.err; echo "default rc $?"
 python bench.py --int16 --no-cpu > $O/r05_bench_int16.json 2>/dev/null
-PF_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu > $O/r05_default_2ranks_gloo_one_gpu.json 2> $O/r05_2ranks.err; echo "2 ranks rc $?"
+PF_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu > $O/r05_default_2ranks_gloo_one_gpu.json 2> $O/r05_2ranks.err; echo "2 ranks rc $?"
 PF_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 4 --steps 20 --warmup 5 --no-cpu --shard strong > $O/r05_strong_4ranks_gloo_one_gpu.json 2> $O/r05_4ranks.err; echo "4 ranks rc $?"
 python - <<'PY'
 import json
