@@ -73,3 +73,100 @@ def map_digest(m):
             l, w = m.tile_level(ix, iy, lv)
             out["%d,%d,%d" % (ix, iy, lv)] = [sha(l), sha(w)]
     return out
+
+
+HOSTILE_KINDS = ("const", "white", "checker1", "checker2", "impulse", "step", "ramp", "noise")
+CONST_COLOURS = ((0, 0, 0), (255, 255, 255), (255, 0, 37), (0, 255, 200), (128, 64, 255), (1, 254, 0))
+
+
+def hostile_frame(kind, rows, cols, k, step_col=None, step_row=None):
+    """BGR8 frames at the edges of the int16 pyramid's ranges (kernels.hip, the bounds of the packed 16-bit stages) and of the 8U
+    clamp, as opposed to the uniform noise of the other parity tests (kept here as the control, kind "noise"):
+      const     one colour per keyframe (CONST_COLOURS[k % 6]: black, white, saturated mixes)
+      white     all 255: every 5-tap sum at 255*16, every vertical sum at 65280
+      checker1  0/255 checkerboard of 1-px cells, checker2 of 2-px cells; channel c shifted by c cells (and by k)
+      impulse   single 255 pixels on 0: the four corners, the middle of each edge (REFLECT taps) and a sparse interior lattice
+      step      0 left of column step_col, 255 from it on, and in channel 1 the same on row step_row (defaults: the middle)
+      ramp      0..255 along x in channel 0, along y in channel 1, along x+y in channel 2"""
+    y, x = np.mgrid[0:rows, 0:cols]
+    out = np.zeros((rows, cols, 3), np.uint8)
+    if kind == "const":
+        out[:] = CONST_COLOURS[k % len(CONST_COLOURS)]
+    elif kind == "white":
+        out[:] = 255
+    elif kind in ("checker1", "checker2"):
+        p = 1 if kind == "checker1" else 2
+        for c in range(3):
+            out[:, :, c] = (((x + c * p + k) // p + y // p) & 1) * 255
+    elif kind == "impulse":
+        for c in range(3):
+            pts = [(0, 0), (0, cols - 1), (rows - 1, 0), (rows - 1, cols - 1),
+                   (0, cols // 2), (rows - 1, cols // 2), (rows // 2, 0), (rows // 2, cols - 1)]
+            for r, q in pts:
+                out[r, q, c] = 255
+            out[5 + c + k:rows - 2:13, 7 + 2 * c:cols - 2:11, c] = 255
+    elif kind == "step":
+        sc = cols // 2 if step_col is None else step_col
+        sr = rows // 2 if step_row is None else step_row
+        out[:, sc:, 0] = 255
+        out[sr:, :, 1] = 255
+        out[:, sc:, 2] = 255
+        out[sr:, :, 2] = 255 - out[sr:, :, 2]
+    elif kind == "ramp":
+        out[:, :, 0] = (x * 255) // max(cols - 1, 1)
+        out[:, :, 1] = (y * 255) // max(rows - 1, 1)
+        out[:, :, 2] = ((x + y) * 255) // max(rows + cols - 2, 1)
+    elif kind == "noise":
+        return workloads().noise_frame(rows, cols, 500 + k)
+    else:
+        raise ValueError(kind)
+    return out
+
+
+def feed_with_model(o, m, img, pose):
+    """Feed one keyframe to the oracle and hand the model the geometry of that feed (the grid after it, the footprint in plane
+    coordinates, M): the model computes its tile range and canvas points itself and must land on the oracle's canvas."""
+    ok = o.feed(img, pose)
+    if ok:
+        dims, M = o.last_canvas()
+        m.feed(img, o.grid(), o.footprint(pose), M)
+        assert m.last[0] == dims, ("tile range", m.last[0], dims)
+    return ok
+
+
+def compare_with_model(x, m, blends=True):
+    """A whole map x (HIP or oracle) against the model: every tile and level (Laplacian and weight), blend_tile_raw and blend_tile of
+    every tile, and the saved mosaic with its origin.  Returns a list of mismatch strings."""
+    bad = []
+    if x.tiles() != m.tiles():
+        return ["tile sets differ: %d vs model %d" % (len(x.tiles()), len(m.tiles()))]
+    for (ix, iy) in m.tiles():
+        for lv in range(m.num_levels):
+            (xl, xw), (ml, mw) = x.tile_level(ix, iy, lv), m.tile_level(ix, iy, lv)
+            if not np.array_equal(xw, mw):
+                bad.append("weight (%d,%d) level %d: %d px differ" % (ix, iy, lv, int((xw != mw).sum())))
+            if not np.array_equal(xl, ml):
+                bad.append("lap (%d,%d) level %d: %d values differ, max |d| %g" %
+                           (ix, iy, lv, int((xl != ml).sum()), float(np.abs(xl.astype(np.float64) - ml).max())))
+        if blends:
+            xr, mr = x.blend_tile_raw(ix, iy), m.blend_tile_raw(ix, iy)
+            if not np.array_equal(xr, mr):
+                bad.append("blend_tile_raw (%d,%d): %d values differ, max |d| %g" %
+                           (ix, iy, int((xr != mr).sum()), float(np.abs(xr.astype(np.float64) - mr).max())))
+            if not np.array_equal(x.blend_tile(ix, iy), m.blend_tile(ix, iy)):
+                bad.append("blend_tile (%d,%d)" % (ix, iy))
+    if blends:
+        xs = x.save_to_memory() if hasattr(x, "save_to_memory") else x.save()
+        ms = m.save()
+        if xs[1] != ms[1] or xs[0].shape != ms[0].shape:
+            bad.append("save: origin %s shape %s vs model %s %s" % (xs[1], xs[0].shape, ms[1], ms[0].shape))
+        elif not np.array_equal(xs[0], ms[0]):
+            bad.append("save: %d px differ" % int((xs[0] != ms[0]).any(axis=2).sum()))
+    return bad
+
+
+def neighbourhoods(tiles):
+    """(tiles with all nine of their 3x3 neighbourhood present, tiles without)"""
+    s = set(tiles)
+    full = [t for t in tiles if all((t[0] + dx, t[1] + dy) in s for dx in (-1, 0, 1) for dy in (-1, 0, 1))]
+    return full, [t for t in tiles if t not in full]

@@ -6,71 +6,8 @@ import numpy as np
 import pytest
 
 
-# ---------------------------------------------------------------- independent numpy restatements
-def np_pyr_down_int(src):
-    """5x5 [1 4 6 4 1]^2, REFLECT_101, ((v+128)>>8) -- exact integer arithmetic."""
-    s = src.astype(np.int64)
-    p = np.pad(s, ((2, 2), (2, 2), (0, 0)), mode="reflect")
-    k = np.array([1, 4, 6, 4, 1], np.int64)
-    h = sum(k[j] * p[:, j:j + s.shape[1]:1] for j in range(5))[:, ::2]
-    h = h[:, :(s.shape[1] + 1) // 2]
-    v = sum(k[j] * h[j:j + s.shape[0]] for j in range(5))[::2][:(s.shape[0] + 1) // 2]
-    return ((v + 128) >> 8).astype(np.int16)
-
-
-def np_pyr_up_int(src):
-    """pyrUp to 2x: even = p[x-1]+6p[x]+p[x+1], odd = 4(p[x]+p[x+1]); index -1 -> 1, n -> n-1."""
-    s = src.astype(np.int64)
-
-    def up_axis(a, axis):
-        a = np.moveaxis(a, axis, 0)
-        n = a.shape[0]
-        prev = a[[1 if n > 1 else 0] + list(range(0, n - 1))]
-        nxt = a[list(range(1, n)) + [n - 1]]
-        out = np.empty((2 * n,) + a.shape[1:], np.int64)
-        out[0::2] = prev + 6 * a + nxt
-        out[1::2] = 4 * (a + nxt)
-        return np.moveaxis(out, 0, axis)
-
-    v = up_axis(up_axis(s, 1), 0)
-    return ((v + 32) >> 6).astype(np.int16)
-
-
-def np_warp_linear_reflect(src, M0, drows, dcols, as_float):
-    """warpPerspective LINEAR/REFLECT with the 64-wide block-relative coordinates, vectorised."""
-    M = np.linalg.inv(np.asarray(M0, np.float64))      # only used with exactly invertible test matrices
-    srows, scols, cn = src.shape
-    y, x = np.mgrid[0:drows, 0:dcols]
-    bw0 = min(1024 // min(16, drows), dcols)
-    xb = (x // bw0) * bw0; x1 = x - xb
-    X0 = M[0, 0] * xb + M[0, 1] * y + M[0, 2]
-    Y0 = M[1, 0] * xb + M[1, 1] * y + M[1, 2]
-    W0 = M[2, 0] * xb + M[2, 1] * y + M[2, 2]
-    W = W0 + M[2, 0] * x1
-    W = np.where(W != 0, 32.0 / np.where(W != 0, W, 1), 0.0)
-    X = np.rint(np.clip((X0 + M[0, 0] * x1) * W, -2 ** 31, 2 ** 31 - 1)).astype(np.int64)
-    Y = np.rint(np.clip((Y0 + M[1, 0] * x1) * W, -2 ** 31, 2 ** 31 - 1)).astype(np.int64)
-    sx = np.clip(X >> 5, -32768, 32767); sy = np.clip(Y >> 5, -32768, 32767)
-    fx = ((X & 31).astype(np.float32) * np.float32(1 / 32)); fy = ((Y & 31).astype(np.float32) * np.float32(1 / 32))
-
-    def refl(p, n):
-        p = np.mod(p, 2 * n)
-        return np.where(p < n, p, 2 * n - 1 - p)
-
-    x0, x1_, y0, y1 = refl(sx, scols), refl(sx + 1, scols), refl(sy, srows), refl(sy + 1, srows)
-    one = np.float32(1)
-    w = [(one - fy) * (one - fx), (one - fy) * fx, fy * (one - fx), fy * fx]
-    s = src.astype(np.float32)
-    out = np.empty((drows, dcols, cn), np.float32)
-    for k in range(cn):
-        t = s[y0, x0, k] * w[0]
-        t = t + s[y0, x1_, k] * w[1]
-        t = t + s[y1, x0, k] * w[2]
-        t = t + s[y1, x1_, k] * w[3]
-        out[:, :, k] = t
-    if as_float:
-        return out
-    return np.clip(np.rint(out.astype(np.float64)), -32768, 32767).astype(np.int16)
+# the independent numpy restatements live in map_model.py, the whole-map model built on them
+from map_model import np_pyr_down_int, np_pyr_up_int, np_warp_linear_reflect
 
 
 # ---------------------------------------------------------------- pyrDown / pyrUp
