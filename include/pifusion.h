@@ -116,11 +116,25 @@ unsigned pf_queue_size(pf_map* m);
  * device stream (no reference counterpart: the reference is synchronous on the CPU).  Returns 0 if a render failed.       */
 int     pf_sync(pf_map* m);
 /* Map2D::save(filename), MultiBandMap2DCPU.cpp:779-847.  Writes PNG (.png),
+ * JPEG (.jpg / .jpeg, either case: quality 95, 4:2:0, cv::imwrite's default;
+ * the collapsed mosaic is encoded on the GPU and only the stream comes back;
+ * a mosaic of more than 65535 pixels a side returns 0 and writes no file),
  * else binary PPM.                                                         */
 int     pf_save(pf_map* m, const char* filename);
 /* The file leg of save() alone: cv::imwrite(filename, result), MultiBandMap2DCPU.cpp:841.  8-bit BGR in,
- * PNG (8-bit RGB, deflate) when the name ends in .png/.PNG, binary PPM (P6) otherwise.  No device needed. */
+ * PNG (8-bit RGB, deflate) when the name ends in .png/.PNG, JPEG (pf_jpeg_encode_bgr at quality 95) when it ends in
+ * .jpg/.jpeg in either case, binary PPM (P6) otherwise.  No device needed. */
 int     pf_write_image(const char* filename, const uint8_t* bgr, int rows, int cols);
+/* cv::imencode(".jpg") / the JPEG leg of cv::imwrite of OpenCV 2.4.9: baseline JPEG, byte for byte what libjpeg writes after
+ * jpeg_set_defaults, JCS_RGB input and jpeg_set_quality(quality, TRUE) -- JFIF 1.01, 4:2:0, the Annex K tables, one interleaved
+ * scan, integer colour conversion and ISLOW DCT.  bgr: rows x cols 8-bit BGR, `step` bytes per row (0 = packed).  quality is
+ * clamped to 1...100.  out = NULL: *len = an upper bound of the stream for any content.  Otherwise *len = the stream's length,
+ * and the stream is in `out` if it fits `cap` (0 + pf_last_error() if not; nothing is written then).  Host code, no device. */
+int     pf_jpeg_encode_bgr(const uint8_t* bgr, int rows, int cols, size_t step, int quality, uint8_t* out, size_t cap, size_t* len);
+/* The same encoder on the GPU (csrc/jpeg_encode.hip), byte-equal to pf_jpeg_encode_bgr, for an image in device memory: the
+ * counterpart of pf_jpeg_decode_device.  The passes run in the order of `hip_stream` (a hipStream_t, NULL = the default stream);
+ * only the stream crosses to the host, and the call returns when `out` (host memory, pinned or not) holds it. */
+int     pf_jpeg_encode_device(const void* dev_bgr, int rows, int cols, size_t step, int quality, uint8_t* out, size_t cap, size_t* len, void* hip_stream);
 /* Input side of the file driver: the reference reads each keyframe with cv::imread(imgfile), backup/map2dfusion.cpp:129-132
  * (8-bit BGR, EXIF orientation ignored as OpenCV 2.4.9 does).  JPEG (baseline, extended and progressive Huffman; grey or
  * YCbCr/RGB; libjpeg's default ISLOW IDCT, fancy upsampling and colour tables, byte-equal to libjpeg-turbo), PNG (non-interlaced;
@@ -178,6 +192,11 @@ int     pf_blend_changed(pf_map* m, int* xy, uint8_t* bgr, int cap);
  * re-draws a region calls.  bgr: n x 256 x 256 x 3; a tile without pyramid leaves its 196 608 bytes untouched.  One launch
  * per 1024 tiles.  Returns 1 / 0.                                           */
 int     pf_blend_tiles(pf_map* m, const int* xy, int n, uint8_t* bgr);
+/* pf_blend_tiles whose results leave as n independent JPEG streams (256 x 256 each, what pf_jpeg_encode_bgr gives for the tile),
+ * packed back to back: stream i is out[offsets[i] .. offsets[i + 1]), offsets has n + 1 entries.  The tiles stay in HBM; one
+ * encode pass per blend launch covers all its tiles.  A tile without pyramid gives an empty range.  0 + pf_last_error() when the
+ * streams do not fit `cap` (pf_jpeg_encode_bgr's bound for 256 x 256, times n, always fits). */
+int     pf_blend_tiles_jpeg(pf_map* m, const int* xy, int n, int quality, uint8_t* out, size_t cap, size_t* offsets);
 /* Page-locked host memory for the output side: results written into such a buffer (pf_blend_changed, pf_blend_tiles,
  * pf_save_to_memory) are copied from HBM straight into it; any other buffer is filled through the library's own pinned
  * staging ring and a host copy (the counterpart of cv::Mat's allocator for the textures updateTexture hands to GL).       */

@@ -104,6 +104,10 @@ def lib():
     L.pf_jpeg_decode_bgr.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_int, C.c_int]
     L.pf_jpeg_decode_device.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_int, C.c_int, vp]
     L.pf_feed_jpeg.argtypes = [vp, C.c_char_p, C.c_size_t, dp]
+    if hasattr(L, "pf_jpeg_encode_bgr") or not os.environ.get("PF_LIB"):
+        L.pf_jpeg_encode_bgr.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.pf_jpeg_encode_device.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+        L.pf_blend_tiles_jpeg.argtypes = [vp, ip, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pf_debug_jpeg_huffman.argtypes = [vp, C.POINTER(C.c_longlong)]; L.pf_debug_jpeg_huffman.restype = None
     L.pf_feed_jpeg_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), dp, C.c_int, ip]
     L.pf_num_levels.argtypes = [vp]
@@ -232,7 +236,7 @@ def perspective_transform(src, dst):
 
 
 def write_image(filename, bgr):
-    """cv::imwrite leg of save() (MultiBandMap2DCPU.cpp:841): HxWx3 BGR uint8 -> .png / .ppm"""
+    """cv::imwrite leg of save() (MultiBandMap2DCPU.cpp:841): HxWx3 BGR uint8 -> .png / .jpg, .jpeg (quality 95, 4:2:0) / .ppm"""
     a = np.ascontiguousarray(bgr, dtype=np.uint8)
     return bool(lib().pf_write_image(filename.encode(), a.ctypes.data, a.shape[0], a.shape[1]))
 
@@ -274,6 +278,36 @@ def decode_jpeg_device(data, dev_ptr, rows, cols, stream=None):
     L = lib(); b = bytes(data)
     if not L.pf_jpeg_decode_device(b, len(b), dev_ptr, rows, cols, stream):
         raise ValueError("decode_jpeg_device: %s" % L.pf_last_error().decode())
+
+
+def jpeg_encode(bgr, quality=95):
+    """cv::imencode(".jpg")-style entry: HxWx3 BGR uint8 (rows may be padded: any array whose pixels are contiguous) -> the bytes
+    of the baseline JPEG stream libjpeg writes for it (4:2:0, Annex K tables, quality as jpeg_set_quality takes it), byte for byte."""
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(bgr, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("jpeg_encode: HxWx3 expected")
+    L = lib(); n = C.c_size_t(0)
+    if not L.pf_jpeg_encode_bgr(a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], quality, None, 0, C.byref(n)):
+        raise ValueError("jpeg_encode: %s" % L.pf_last_error().decode())
+    out = np.empty(n.value, np.uint8)
+    if not L.pf_jpeg_encode_bgr(a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], quality, out.ctypes.data, out.size, C.byref(n)):
+        raise ValueError("jpeg_encode: %s" % L.pf_last_error().decode())
+    return out[:n.value].tobytes()
+
+
+def jpeg_encode_device(dev_ptr, rows, cols, quality=95, step=0, stream=None):
+    """The same encoder on the GPU (csrc/jpeg_encode.hip) for rows x cols BGR8 pixels at the device address `dev_ptr`, `step` bytes
+    per row (0 = packed), its passes in the order of `stream` (a hipStream_t handle; None = the default stream).  Returns the bytes
+    of the stream: byte-equal to jpeg_encode."""
+    L = lib(); n = C.c_size_t(0)
+    if not L.pf_jpeg_encode_device(dev_ptr, rows, cols, step, quality, None, 0, C.byref(n), stream):
+        raise ValueError("jpeg_encode_device: %s" % L.pf_last_error().decode())
+    out = np.empty(n.value, np.uint8)
+    if not L.pf_jpeg_encode_device(dev_ptr, rows, cols, step, quality, out.ctypes.data, out.size, C.byref(n), stream):
+        raise ValueError("jpeg_encode_device: %s" % L.pf_last_error().decode())
+    return out[:n.value].tobytes()
 
 
 def jpeg_huffman_counts(map2d=None):
@@ -464,6 +498,24 @@ class Map2D:
         if out is None:
             out = np.zeros((n, ELE_PIXELS, ELE_PIXELS, 3), np.uint8)
         return out[:n] if lib().pf_blend_tiles(self._h, xy, n, out.ctypes.data) else None
+
+    def blend_tiles_jpeg(self, tiles, quality=95, cap=None):
+        """blend_tiles whose results leave as JPEG streams (256 x 256 each, encoded on the GPU from where the blend left them):
+        a list of bytes, one per tile, empty for a tile without pyramid; None on failure.  cap: bytes of the buffer the
+        streams are packed into (default: the bound for any content)."""
+        n = len(tiles)
+        xy = (C.c_int * (2 * n))(*[v for t in tiles for v in t])
+        L = lib()
+        if cap is None:
+            b = C.c_size_t(0); one = np.zeros(3, np.uint8)
+            L.pf_jpeg_encode_bgr(one.ctypes.data, ELE_PIXELS, ELE_PIXELS, 0, quality, None, 0, C.byref(b))
+            cap = b.value * n
+        out = np.empty(cap + 1, np.uint8); out[cap] = 0xA5
+        off = (C.c_size_t * (n + 1))()
+        if not L.pf_blend_tiles_jpeg(self._h, xy, n, quality, out.ctypes.data, cap, off):
+            return None
+        assert out[cap] == 0xA5
+        return [out[off[i]:off[i + 1]].tobytes() for i in range(n)]
 
     # ---- multi-GPU seam exchange
     def halo_bytes(self, dx, dy):

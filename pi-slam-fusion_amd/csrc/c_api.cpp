@@ -109,6 +109,41 @@ int pf_jpeg_decode_device(const uint8_t* data, size_t len, void* dev_bgr, int ro
     if (at.device != prev) (void)hipSetDevice(prev);
     return ok;
 }
+// pf_jpeg_encode_device's encoder: one per device, as the decoder's
+static pf::JpegEncoder* shared_jpeg_encoder(int device)
+{
+    static pf::JpegEncoder* e[64] = {};
+    if (device < 0 || device >= 64) device = 0;
+    if (!e[device]) e[device] = new pf::JpegEncoder();
+    return e[device];
+}
+int pf_jpeg_encode_device(const void* dev_bgr, int rows, int cols, size_t step, int quality, uint8_t* out, size_t cap, size_t* len, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_jpeg_mu);
+    if (!dev_bgr || !len || rows <= 0 || cols <= 0) { pf::set_error("pf_jpeg_encode_device: no image, no length or a size that is not positive"); return 0; }
+    if (!pf::jpeg_size_ok("pf_jpeg_encode_device", rows, cols)) return 0;
+    if (step == 0) step = (size_t)cols * 3;
+    if (step < (size_t)cols * 3) { pf::set_error("pf_jpeg_encode_device: step is smaller than a row"); return 0; }
+    if (!out) { *len = pf::jenc::stream_bound(rows, cols); return 1; }
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dev_bgr) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_jpeg_encode_device: the image is not in device memory"); return 0; }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_jpeg_encode_device: hipSetDevice failed"); return 0; }
+    pf::JpegEncoder* e = shared_jpeg_encoder(at.device);
+    size_t off[2] = { 0, 0 };
+    int ok = e->encode(dev_bgr, 1, nullptr, 0, rows, cols, step, quality, off, hip_stream);
+    if (ok) {
+        *len = off[1];
+        if (off[1] > cap) {
+            pf::set_error("pf_jpeg_encode_device: the stream has " + std::to_string(off[1]) + " bytes, the buffer " + std::to_string(cap));
+            (void)hipStreamSynchronize((hipStream_t)hip_stream);
+            ok = 0;
+        } else ok = e->fetch(out, hip_stream);
+    }
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
 void pf_debug_jpeg_huffman(pf_map* m, long long out[3])
 {
     if (!out) return;
@@ -173,6 +208,13 @@ int pf_blend_tiles(pf_map* m, const int* xy, int n, uint8_t* bgr)
     std::vector<std::pair<int, int>> tiles(n);
     for (int i = 0; i < n; i++) tiles[i] = { xy[2 * i], xy[2 * i + 1] };
     return m->impl.blend_list(tiles, bgr);
+}
+int pf_blend_tiles_jpeg(pf_map* m, const int* xy, int n, int quality, uint8_t* out, size_t cap, size_t* offsets)
+{
+    if (!m || !xy || !out || !offsets || n <= 0) { pf::set_error("pf_blend_tiles_jpeg: no map, no tiles or no buffer"); return 0; }
+    std::vector<std::pair<int, int>> tiles(n);
+    for (int i = 0; i < n; i++) tiles[i] = { xy[2 * i], xy[2 * i + 1] };
+    return m->impl.blend_list_jpeg(tiles, quality, out, cap, offsets);
 }
 void* pf_host_alloc(size_t bytes)
 {

@@ -375,18 +375,18 @@ int DistMap::blend_changed(int* xy, uint8_t* bgr, int cap)
 
 // save() across ranks: tiles travel once to rank 0, which collapses the whole mosaic (.cpp:779-847).  On the other ranks the
 // call returns true with rows = cols = 0 (they hold no picture).
-bool DistMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
+bool DistMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const char* jpeg)
 {
     const auto t_begin = std::chrono::steady_clock::now();
     if (!m_->use_device()) return false;
     const int n = t_->nranks, me = t_->rank;
-    if (n == 1) return m_->save_to_memory(bgr, rows, cols, tx0, ty0);
+    if (n == 1) return m_->save_to_memory(bgr, rows, cols, tx0, ty0, nullptr, jpeg);
     std::vector<std::vector<FusionMap::TileRec>> all;
     std::vector<long long> caps;
     if (!gather_lists(all, caps, 0)) return false;
     const size_t nb = m_->tile_bytes();
     // query (bgr == nullptr): the extent is known from the lists alone
-    if (!bgr) {
+    if (!bgr && !jpeg) {
         int mnx = 1 << 30, mny = 1 << 30, mxx = -(1 << 30), mxy = -(1 << 30), cnt = 0;
         for (auto& l : all) for (auto& t : l) { cnt++; mnx = std::min(mnx, t.ix); mny = std::min(mny, t.iy); mxx = std::max(mxx, t.ix); mxy = std::max(mxy, t.iy); }
         if (!cnt) return false;
@@ -419,7 +419,7 @@ bool DistMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* 
     std::vector<FusionMap::ForeignTile> foreign;
     for (int p = 1; p < n; p++)
         for (size_t k = 0; k < all[p].size(); k++) foreign.push_back({ all[p][k].ix, all[p][k].iy, (char*)recv_.p + off[p] + k * nb });
-    const bool ok = m_->save_to_memory(bgr, rows, cols, tx0, ty0, &foreign);
+    const bool ok = m_->save_to_memory(bgr, rows, cols, tx0, ty0, &foreign, jpeg);
     stats_.bytes_received = total; stats_.tiles = foreign.size();
     stats_.exchange_ms = std::chrono::duration<double, std::milli>(t_x - t_begin).count();
     stats_.compute_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_x).count();
@@ -475,6 +475,12 @@ bool DistMap::save(const char* filename)
 {
     int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
     if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
+    if (is_jpeg_name(filename) && !m_->single_band()) {          // rank 0 encodes the gathered mosaic on its GPU (every rank takes this branch: the exchange is collective)
+        if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0, filename)) return false;          // rank 0's map writes the file
+        if (t_->rank != 0) return true;
+        std::printf("Resolution:[%d %d]\n", cols, rows);
+        return true;
+    }
     std::vector<uint8_t> img((size_t)rows * cols * 3 + 1);
     if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
     if (t_->rank != 0) return true;

@@ -27,7 +27,7 @@ public:
     DistMap(FusionMap* m, Transport* t);      // takes the transport
     ~DistMap();
     int  blend_changed(int* xy, uint8_t* bgr, int cap);        // tiles blended on this rank, -1 on failure
-    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0);
+    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const char* jpeg_file = nullptr);      // jpeg_file: see FusionMap::save_to_memory
     bool save(const char* filename);
     // 1 rendered / accepted, 0 rejected, -1 failure.  `produce` (root only, img->data == nullptr): the root's pixels are written into its
     // staged slot by the caller's own work on the map's stream (pf_dist_feed_jpeg: the decoder) instead of being uploaded

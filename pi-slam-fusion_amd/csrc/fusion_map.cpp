@@ -231,6 +231,7 @@ FusionMap::~FusionMap()
     if (out_ready_) (void)hipEventDestroy(out_ready_);
     if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
     blend_src_.release(); blend_out_raw_.release(); blend_out_bgr_.release(); mosaic_table_.release(); w8_.release(); wmap_.release();
+    jpeg_enc_.release();
     store_.clear();
     (void)hipStreamDestroy(stream_);
 }
@@ -2007,13 +2008,15 @@ bool FusionMap::download(const std::vector<OutPiece>& pieces)
 // sets for neighbours held by other shards.  Results land in tile order (a tile that does not exist leaves the caller's
 // bytes alone).  One launch of the fused collapse kernel per kBlendLaunch tiles, "blend with neighbours" and "blend by self"
 // tiles side by side in it; the pixels come back through download().
-bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host)
+bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg)
 {
     Section sec(this, T_UPDATE_TEXTURE);
 #if PF_EXPERIMENTS
     static const bool per_level = exp_env("PF_BLEND_PER_LEVEL") != nullptr;
-    if (per_level) return blend_batch_per_level(tiles, halo9, raw_host, bgr_host);
+    if (per_level && !jpeg) return blend_batch_per_level(tiles, halo9, raw_host, bgr_host);
 #endif
+    const bool want_bgr = bgr_host || jpeg;
+    if (jpeg) { jpeg->used = 0; jpeg->offsets[0] = 0; }
     const int nl = band_num_ + 1;
     const size_t es = lay_.f32 ? 4 : 2, px = 3 * es;
     const size_t tile_px = (size_t)kElePixels * kElePixels;
@@ -2022,7 +2025,7 @@ bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const
     // neighbour pixels the crop depends on at levels >= 1 (pyrUp reaches one pixel per level: collapse_fused.hip)
     double tile_bytes[2] = { 0, 0 };
     for (int nb = 0; nb < 2; nb++) {
-        double b = (double)tile_px * 4 + (raw_host ? (double)tile_px * px : 0) + (bgr_host ? (double)tile_px * 3 : 0);
+        double b = (double)tile_px * 4 + (raw_host ? (double)tile_px * px : 0) + (want_bgr ? (double)tile_px * 3 : 0);
         int lo = 0, hi = kElePixels - 1;
         for (int i = 0; i < nl; i++) {
             const int ts = kElePixels >> i;
@@ -2057,16 +2060,37 @@ bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const
             jobs.push_back(jb);
             bytes += tile_bytes[jb.border];
         }
-        if (jobs.empty()) continue;
+        if (jobs.empty()) { if (jpeg) for (size_t t = c0; t < c0 + cn; t++) jpeg->offsets[t + 1] = jpeg->used; continue; }
         if (raw_host && !blend_out_raw_.reserve(tile_px * px * cn)) return false;
-        if (bgr_host && !blend_out_bgr_.reserve(tile_px * 3 * cn)) return false;
+        if (want_bgr && !blend_out_bgr_.reserve(tile_px * 3 * cn)) return false;
         if (!blend_src_.reserve(jobs.size() * sizeof(BlendJob))) return false;
         HIP_OK(hipMemcpyAsync(blend_src_.p, jobs.data(), jobs.size() * sizeof(BlendJob), hipMemcpyHostToDevice, stream_));
         prof_begin(K_BLEND_FUSED, bytes);
         launch_blend_fused(stream_, lay_, (const BlendJob*)blend_src_.p, (int)jobs.size(), raw_host ? blend_out_raw_.p : nullptr,
-                           bgr_host ? (uint8_t*)blend_out_bgr_.p : nullptr);
+                           want_bgr ? (uint8_t*)blend_out_bgr_.p : nullptr);
         prof_end();
         HIP_OK(hipGetLastError());
+        if (jpeg) {
+            // one encode pass over the launch's tiles where they lie in HBM; only the streams come back.  A tile without
+            // pyramid has no job: its range is empty
+            std::vector<int> slots(jobs.size());
+            for (size_t a = 0; a < jobs.size(); a++) slots[a] = jobs[a].out;
+            std::vector<size_t> off(jobs.size() + 1);
+            if (!jpeg_enc_.encode(blend_out_bgr_.p, (int)jobs.size(), slots.data(), tile_px * 3, kElePixels, kElePixels, (size_t)kElePixels * 3, jpeg->quality, off.data(), stream_)) return false;
+            if (jpeg->used + off.back() > jpeg->cap) {
+                set_error("pf_blend_tiles_jpeg: the streams need more than the " + std::to_string(jpeg->cap) + " bytes of the buffer");
+                HIP_OK(hipStreamSynchronize(stream_));
+                return false;
+            }
+            if (!jpeg_enc_.fetch(jpeg->out + jpeg->used, stream_)) return false;          // returns with the stream drained: jobs (pageable) have been read
+            size_t a = 0;
+            for (size_t t = c0; t < c0 + cn; t++) {
+                if (a < jobs.size() && (size_t)jobs[a].out == t - c0) a++;
+                jpeg->offsets[t + 1] = jpeg->used + off[a];
+            }
+            jpeg->used += off.back();
+            continue;
+        }
         // runs of tiles that exist, each one piece per output
         std::vector<OutPiece> pieces;
         for (size_t a = 0; a < jobs.size();) {
@@ -2199,6 +2223,26 @@ bool FusionMap::blend_list(const std::vector<std::pair<int, int>>& tiles, uint8_
     return blend_batch(tiles, nullptr, nullptr, bgr);
 }
 
+bool FusionMap::blend_list_jpeg(const std::vector<std::pair<int, int>>& tiles, int quality, uint8_t* out, size_t cap, size_t* offsets)
+{
+    if (single_band_) {          // the Map2DCPU tile is displayable as is (see blend_tile): assembled on the host, the host encoder
+        std::vector<uint8_t> px((size_t)kElePixels * kElePixels * 3), stream;
+        offsets[0] = 0;
+        for (size_t i = 0; i < tiles.size(); i++) {
+            stream.clear();
+            if (blend_tile(tiles[i].first, tiles[i].second, nullptr, px.data(), nullptr)) jenc::encode_bgr(px.data(), kElePixels, kElePixels, (size_t)kElePixels * 3, quality, stream);
+            if (offsets[i] + stream.size() > cap) { set_error("pf_blend_tiles_jpeg: the streams need more than the " + std::to_string(cap) + " bytes of the buffer"); return false; }
+            std::memcpy(out + offsets[i], stream.data(), stream.size());
+            offsets[i + 1] = offsets[i] + stream.size();
+        }
+        return init_ok_;
+    }
+    std::lock_guard<std::mutex> l(mu_); (void)drain();
+    if (!init_ok_ || !set_device()) return false;
+    TileJpeg tj{ quality, out, cap, offsets };
+    return blend_batch(tiles, nullptr, nullptr, nullptr, &tj);
+}
+
 // the draw() loop's texture refresh (.cpp:705-742) without GL
 int FusionMap::blend_changed(int* xy, uint8_t* bgr, int cap)
 {
@@ -2237,7 +2281,7 @@ int FusionMap::blend_changed(int* xy, uint8_t* bgr, int cap)
 // ------------------------------------------------------------------- save
 // MultiBandMap2DCPU::save (.cpp:779-847): paste all tiles per level, collapse
 // the whole mosaic once, 8U, background where level-0 weight is 0.
-bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const std::vector<ForeignTile>* foreign)
+bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const std::vector<ForeignTile>* foreign, const char* jpeg)
 {
     std::lock_guard<std::mutex> l(mu_); (void)drain();
     if (!init_ok_ || !valid_ || !set_device()) return false;
@@ -2253,7 +2297,9 @@ bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int
     if (!cnt) return false;
     const int wx = mxx + 1 - mnx, wy = mxy + 1 - mny;
     *rows = wy * kElePixels; *cols = wx * kElePixels; *tx0 = mnx; *ty0 = mny;
-    if (!bgr) return true;
+    if (!bgr && !jpeg) return true;
+    if (jpeg && (bgr || single_band_)) { set_error("save: the stream of a mosaic in HBM was asked for where there is none"); return false; }
+    if (jpeg && !jpeg_size_ok("save", *rows, *cols)) return false;
     if (single_band_) {          // Map2DCPU::save (Map2DCPU.cpp:523-563): paste the tiles; holes are zero here
         HIP_OK(sync_all());
         std::memset(bgr, 0, (size_t)*rows * *cols * 3);
@@ -2310,6 +2356,12 @@ bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int
     launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
     prof_end();
     HIP_OK(hipGetLastError());
+    if (jpeg) {          // the mosaic stays where the collapse left it; cv::imwrite's JPEG defaults: quality 95, 4:2:0
+        size_t off[2];
+        if (!jpeg_enc_.encode(blend_out_bgr_.p, 1, nullptr, 0, *rows, *cols, (size_t)*cols * 3, 95, off, stream_)) return false;
+        const uint8_t* stream = jpeg_enc_.fetch_pinned(stream_);
+        return stream && write_bytes_file(jpeg, stream, off[1]);
+    }
     if (!download({ { bgr, blend_out_bgr_.p, out_bytes } })) return false;
     return true;
 }
@@ -2318,6 +2370,12 @@ bool FusionMap::save(const char* filename)
 {
     int rows, cols, tx0, ty0;
     if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
+    if (is_jpeg_name(filename) && !single_band_) {          // multi-band: encoded on the GPU, only the stream is copied and written
+        if (!jpeg_size_ok("save", rows, cols)) return false;
+        if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0, nullptr, filename)) return false;
+        std::printf("Resolution:[%d %d]\n", cols, rows);
+        return true;
+    }
     std::vector<uint8_t> img((size_t)rows * cols * 3);
     if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
     if (!write_image_file(filename, img.data(), rows, cols)) return false;

@@ -6,6 +6,7 @@
 #include "kernels.hpp"
 #include "dist_plan.hpp"
 #include "env.hpp"
+#include "jpeg_encode.hpp"
 #include <hip/hip_runtime.h>
 #include <condition_variable>
 #include <cstdlib>
@@ -106,7 +107,9 @@ public:
     bool sync();
     bool save(const char* filename);
     struct ForeignTile { int ix, iy; const void* dev; };          // a tile slot image held outside the store (gathered for save)
-    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const std::vector<ForeignTile>* foreign = nullptr);
+    // jpeg_file (bgr == nullptr): the collapsed mosaic stays in HBM and leaves as the JPEG stream save("x.jpg") writes
+    // (jpeg_encode.hip), which lands in the encoder's page-locked buffer and goes to that file
+    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const std::vector<ForeignTile>* foreign = nullptr, const char* jpeg_file = nullptr);
 
     // seam exchange support (dist.cpp)
     using TileRec = pf::TileRec;        // dist_plan.hpp
@@ -127,6 +130,7 @@ public:
     hipStream_t stream() const { return stream_; }
     int  device() const { return device_; }
     bool use_device() { return set_device(); }
+    bool single_band() const { return single_band_; }
     // draw()'s Fuse2Google gate and operands for tile (ix, iy) (MultiBandMap2DCPU.cpp:709-712, :730-735, :744): false when the tile
     // has no pyramid, or lies on the rim of the dense grid while HighQualityShow is on
     bool map_update_inputs(int ix, int iy, double plane7[7], double mn[2], double* ele, int* x, int* y);
@@ -155,6 +159,9 @@ public:
     bool blend_tile(int ix, int iy, void* raw, uint8_t* bgr, const void* const* halo);
     int  blend_changed(int* xy, uint8_t* bgr, int cap);
     bool blend_list(const std::vector<std::pair<int, int>>& tiles, uint8_t* bgr);      // pf_blend_tiles: Ischanged left alone
+    // pf_blend_tiles_jpeg: the same tiles as n JPEG streams back to back, offsets[0..n]; the blended pixels stay in HBM
+    struct TileJpeg { int quality; uint8_t* out; size_t cap; size_t* offsets; size_t used = 0; };
+    bool blend_list_jpeg(const std::vector<std::pair<int, int>>& tiles, int quality, uint8_t* out, size_t cap, size_t* offsets);
     size_t halo_bytes_for(int dx, int dy) const { return halo_bytes(lay_, dx, dy); }
     bool halo_pack(int ix, int iy, int dx, int dy, void* dev_out);
     size_t tile_bytes() const { return lay_.slot_bytes; }
@@ -182,7 +189,7 @@ private:
     void worker();                                                 // .cpp:619-635
     int  acquire_slot(size_t bytes);
     bool upload(const pf_image* img, int slot);
-    bool blend_batch(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host);
+    bool blend_batch(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg = nullptr);
     // bytes: SURVEY 8d's algorithmic bytes of the launch for EVERY tile of the canvas; bytes_run (< 0: the same): those of the part of the
     // canvas its blocks actually process (the cull / a shard leave blocks out) -- the numerator of bench.py's roofline.frac
     void prof_begin(int id, double bytes, hipStream_t st = nullptr, double bytes_run = -1);
@@ -352,6 +359,7 @@ private:
     DevBuf blend_lv_[kMaxLevels], blend_src_, blend_out_raw_, blend_out_bgr_, mosaic_table_, strip_desc_;
     // results on their way to the host: two pinned staging slots, filled on copy_stream_ while the host empties the other one
     static constexpr size_t kOutSlot = (size_t)32 << 20;
+    JpegEncoder jpeg_enc_;      // save("x.jpg"), pf_blend_tiles_jpeg: reads blend_out_bgr_ on stream_, buffers of its own
     struct OutPiece { void* dst; const void* src; size_t bytes; };      // host destination, device source
     uint8_t*    out_pin_[2]{};
     hipEvent_t  out_copied_[2]{}, out_ready_ = nullptr;
@@ -395,5 +403,8 @@ private:
 
 // PNG (zlib) / PPM writer for save()
 bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int cols);
+bool is_jpeg_name(const char* filename);                                      // image_io.cpp
+bool jpeg_size_ok(const char* who, int rows, int cols);
+bool write_bytes_file(const char* filename, const uint8_t* data, size_t len);
 
 }  // namespace pf

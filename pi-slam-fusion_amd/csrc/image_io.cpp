@@ -1,8 +1,10 @@
 // image_io.cpp -- output side of save(): the reference hands the mosaic to
 // cv::imwrite (MultiBandMap2DCPU.cpp:841).  PNG (8-bit RGB, zlib stream split
-// over IDAT chunks) when the name ends in .png, binary PPM otherwise.
+// over IDAT chunks) when the name ends in .png, JPEG (quality 95, 4:2:0: cv::imwrite's
+// default, jpeg_encode.hpp) when it ends in .jpg / .jpeg, binary PPM otherwise.
 #include "../../include/pifusion.h"
 #include "jpeg_decode.hpp"
+#include "jpeg_encode.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -120,8 +122,43 @@ static bool write_png(FILE* f, const uint8_t* bgr, int rows, int cols)
     return ok && png_chunk(f, "IEND", nullptr, 0);
 }
 
+// the name ends in .jpg / .jpeg, in either case: cv::imwrite hands the image to its JPEG encoder
+bool is_jpeg_name(const char* filename)
+{
+    const size_t n = std::strlen(filename);
+    auto ends = [&](const char* ext) {
+        const size_t k = std::strlen(ext);
+        if (n < k) return false;
+        for (size_t i = 0; i < k; i++) { char c = filename[n - k + i]; if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a'); if (c != ext[i]) return false; }
+        return true;
+    };
+    return ends(".jpg") || ends(".jpeg");
+}
+
+bool jpeg_size_ok(const char* who, int rows, int cols)
+{
+    if (rows <= jenc::kMaxDim && cols <= jenc::kMaxDim) return true;
+    set_error(std::string(who) + ": a JPEG file holds at most 65535 x 65535 pixels, the image has " + std::to_string(cols) + " x " + std::to_string(rows));
+    return false;
+}
+
+bool write_bytes_file(const char* filename, const uint8_t* data, size_t len)
+{
+    FILE* f = std::fopen(filename, "wb");
+    if (!f) { set_error(std::string("save: cannot open ") + filename); return false; }
+    const bool ok = std::fwrite(data, 1, len, f) == len;
+    if (std::fclose(f) != 0 || !ok) { set_error("save: write failed"); return false; }
+    return true;
+}
+
 bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int cols)
 {
+    if (is_jpeg_name(filename)) {          // before the file is opened: an image JPEG cannot hold leaves no file
+        if (!jpeg_size_ok("save", rows, cols)) return false;
+        std::vector<uint8_t> stream;
+        try { jenc::encode_bgr(bgr, rows, cols, (size_t)cols * 3, 95, stream); } catch (const std::bad_alloc&) { set_error("save: out of memory"); return false; }
+        return write_bytes_file(filename, stream.data(), stream.size());
+    }
     FILE* f = std::fopen(filename, "wb");
     if (!f) { set_error(std::string("save: cannot open ") + filename); return false; }
     const size_t n = std::strlen(filename);
@@ -148,6 +185,20 @@ bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int co
 extern "C" {
 int pf_write_image(const char* filename, const uint8_t* bgr, int rows, int cols)
 { return filename && bgr && rows > 0 && cols > 0 && pf::write_image_file(filename, bgr, rows, cols); }
+int pf_jpeg_encode_bgr(const uint8_t* bgr, int rows, int cols, size_t step, int quality, uint8_t* out, size_t cap, size_t* len)
+{
+    if (!bgr || !len || rows <= 0 || cols <= 0) { pf::set_error("pf_jpeg_encode_bgr: no image, no length or a size that is not positive"); return 0; }
+    if (!pf::jpeg_size_ok("pf_jpeg_encode_bgr", rows, cols)) return 0;
+    if (step == 0) step = (size_t)cols * 3;
+    if (step < (size_t)cols * 3) { pf::set_error("pf_jpeg_encode_bgr: step is smaller than a row"); return 0; }
+    if (!out) { *len = pf::jenc::stream_bound(rows, cols); return 1; }
+    std::vector<uint8_t> stream;
+    try { pf::jenc::encode_bgr(bgr, rows, cols, step, quality, stream); } catch (const std::bad_alloc&) { pf::set_error("pf_jpeg_encode_bgr: out of memory"); return 0; }
+    *len = stream.size();
+    if (stream.size() > cap) { pf::set_error("pf_jpeg_encode_bgr: the stream has " + std::to_string(stream.size()) + " bytes, the buffer " + std::to_string(cap)); return 0; }
+    std::memcpy(out, stream.data(), stream.size());
+    return 1;
+}
 int pf_image_info(const char* filename, int* rows, int* cols)
 {
     if (!filename || !rows || !cols) return 0;
