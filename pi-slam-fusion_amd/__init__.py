@@ -384,10 +384,12 @@ class Map2D:
         im = Image(img.shape[0], img.shape[1], typ, img.ctypes.data, step)
         return bool(lib().pf_feed(self._h, C.byref(im), pp))
 
-    def feed_device(self, data_ptr, rows, cols, pose, step=0):
-        """Frame already resident in HBM (e.g. torch tensor .data_ptr())."""
+    def feed_device(self, data_ptr, rows, cols, pose, step=0, channels=3):
+        """Frame already resident in HBM (e.g. torch tensor .data_ptr()): BGR, or BGRA with channels=4 (pf_feed_device takes both)."""
+        if channels not in (3, 4):
+            raise ValueError("feed_device: 3 (BGR) or 4 (BGRA) channels")
         p, pp = _pose(pose)
-        im = Image(rows, cols, PF_8UC3, data_ptr, step)
+        im = Image(rows, cols, PF_8UC3 if channels == 3 else PF_8UC4, data_ptr, step)
         return bool(lib().pf_feed_device(self._h, C.byref(im), pp))
 
     def feed_jpeg(self, data, pose):

@@ -134,6 +134,28 @@ def feed_with_model(o, m, img, pose):
     return ok
 
 
+def feed_single_with_model(o, m, img, pose):
+    """feed_with_model for the single-band pair (OracleMap(single_band=1), ModelMapSingleBand); of a BGRA frame the oracle gets the
+    first three channels, which is what the map takes of it."""
+    ok = o.feed(img[:, :, :3], pose)
+    if ok:
+        dims, M = o.last_canvas()
+        m.feed(img, o.grid(), o.footprint(pose), M)
+        assert m.last[0] == dims, ("tile range", m.last[0], dims)
+    return ok
+
+
+def single_band_pair(orc, cam, poses, frames, prep, weight_type=0, scale=1.0):
+    """OracleMap(single_band=1) and ModelMapSingleBand prepared alike and fed the same keyframes (feed_single_with_model)."""
+    from map_model import ModelMapSingleBand
+    o = orc.OracleMap(single_band=1, weight_type=weight_type, scale=scale)
+    m = ModelMapSingleBand(weight_type)
+    assert o.prepare(workloads().IDENTITY_PLANE, cam, prep)
+    for img, p in zip(frames, poses):
+        assert feed_single_with_model(o, m, img, p)
+    return o, m
+
+
 def compare_with_model(x, m, blends=True):
     """A whole map x (HIP or oracle) against the model: every tile and level (Laplacian and weight), blend_tile_raw and blend_tile of
     every tile, and the saved mosaic with its origin.  Returns a list of mismatch strings."""
@@ -159,6 +181,40 @@ def compare_with_model(x, m, blends=True):
         xs = x.save_to_memory() if hasattr(x, "save_to_memory") else x.save()
         ms = m.save()
         if xs[1] != ms[1] or xs[0].shape != ms[0].shape:
+            bad.append("save: origin %s shape %s vs model %s %s" % (xs[1], xs[0].shape, ms[1], ms[0].shape))
+        elif not np.array_equal(xs[0], ms[0]):
+            bad.append("save: %d px differ" % int((xs[0] != ms[0]).any(axis=2).sum()))
+    return bad
+
+
+def compare_single_with_model(x, m):
+    """A single-band map x (HIP or oracle) against ModelMapSingleBand: the tile set and every tile_bgra; for the HIP map also
+    blend_tile of every tile, blend_tiles of all of them at once and save_to_memory with its origin (the oracle restates none of
+    these for Map2DCPU).  Returns a list of mismatch strings."""
+    bad = []
+    if x.tiles() != m.tiles():
+        return ["tile sets differ: %d vs model %d" % (len(x.tiles()), len(m.tiles()))]
+    tiles = m.tiles()
+    for t in tiles:
+        xt, mt = x.tile_bgra(*t), m.tile_bgra(*t)
+        if xt is None or not np.array_equal(xt, mt):
+            d = None if xt is None else (xt != mt)
+            bad.append("tile_bgra %s: %s" % (t, "missing" if d is None else "%d px differ (%d in alpha)" %
+                                             (int(d.any(axis=2).sum()), int(d[:, :, 3].sum()))))
+    if not hasattr(x, "blend_tiles"):
+        return bad
+    for t in tiles:
+        if not np.array_equal(x.blend_tile(*t), m.blend_tile(*t)):
+            bad.append("blend_tile %s" % (t,))
+    if tiles:
+        for t, im in zip(tiles, x.blend_tiles(tiles)):
+            if not np.array_equal(im, m.blend_tile(*t)):
+                bad.append("blend_tiles %s" % (t,))
+    xs, ms = x.save_to_memory(), m.save()
+    if (xs is None) != (ms is None):
+        bad.append("save: %s vs model %s" % (xs is not None, ms is not None))
+    elif xs is not None:
+        if tuple(xs[1]) != tuple(ms[1]) or xs[0].shape != ms[0].shape:
             bad.append("save: origin %s shape %s vs model %s %s" % (xs[1], xs[0].shape, ms[1], ms[0].shape))
         elif not np.array_equal(xs[0], ms[0]):
             bad.append("save: %d px differ" % int((xs[0] != ms[0]).any(axis=2).sum()))

@@ -1,4 +1,4 @@
-"""An independent numpy model of MultiBandMap2DCPU (Map2DFusion/MultiBandMap2DCPU.cpp), test code only.
+"""Independent numpy models of MultiBandMap2DCPU (Map2DFusion/MultiBandMap2DCPU.cpp) and, at the end, of Map2DCPU, test code only.
 
 Written from SURVEY 3.2/3.3 and 8c rules 2-9 and from reading the reference's renderFrame (.cpp:311-558), Ele::blend (.cpp:77-146)
 and save (.cpp:779-847).  It shares no pixel arithmetic with the oracle (oracle/oracle.c) or the HIP library: the geometry a feed
@@ -244,6 +244,29 @@ def to_8u(raw):
     return np.clip(np.rint((raw * F(255)).astype(np.float64)), 0, 255).astype(np.uint8)
 
 
+def canvas_geometry(shape, grid, footprint, M):
+    """renderFrame's tile range and canvas points (MultiBandMap2DCPU.cpp:380-391, :437-438; Map2DCPU.cpp:219-233, :290-296 are the same
+    lines) from the grid after the feed, the footprint in plane coordinates and M, which must map the frame onto those points.
+    Returns ((off_x, off_y), (x0, y0, x1, y1) as dense tile indices, canvas points as float32, M as 3 x 3 float64)."""
+    (w, h, offx, offy), (mnx, mny, _, _, ele_size, length_pixel) = grid
+    pts = np.asarray(footprint, np.float64).reshape(4, 2)
+    xmin, ymin = pts[:, 0].min(), pts[:, 1].min()
+    xmax, ymax = pts[:, 0].max(), pts[:, 1].max()
+    inv = 1.0 / ele_size                                                        # eleSizeInv
+    x0 = int(math.floor((xmin - mnx) * inv)); y0 = int(math.floor((ymin - mny) * inv))      # .cpp:380-383
+    x1 = int(math.ceil((xmax - mnx) * inv)); y1 = int(math.ceil((ymax - mny) * inv))
+    assert 0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h, "footprint outside the grid it was given"
+    cx, cy = mnx + ele_size * x0, mny + ele_size * y0                           # .cpp:390-391
+    lpi = 1.0 / length_pixel
+    canvas = np.array([[(p[0] - cx) * lpi, (p[1] - cy) * lpi] for p in pts], np.float32)   # Point2f, .cpp:437-438
+    M = np.asarray(M, np.float64).reshape(3, 3)
+    rows, cols = shape[:2]
+    corners = np.array([[0, 0], [cols, 0], [0, rows], [cols, rows]], np.float64)
+    proj = (M @ np.c_[corners, np.ones(4)].T).T
+    assert np.abs(proj[:, :2] / proj[:, 2:] - canvas).max() < 1e-3, "M does not map the frame onto its canvas points"
+    return (offx, offy), (x0, y0, x1, y1), canvas, M
+
+
 # ---------------------------------------------------------------- the map
 class ModelMap:
     """MultiBandMap2DCPU, thread=false, one renderFrame per feed.  Tiles are keyed by world tile (ix, iy) = dense index + grid
@@ -271,24 +294,10 @@ class ModelMap:
         """One keyframe.  grid: (dims, geo) of the map after this feed (dims = [w, h, off_x, off_y], geo = [min_x, min_y, max_x,
         max_y, ele_size, length_pixel]); footprint: the 4 plane points of the frame corners (4 x 2); M: the 3x3 homography from
         the frame to the canvas."""
-        (w, h, offx, offy), (mnx, mny, _, _, ele_size, length_pixel) = grid
         self.grid_ = grid
         self._out = {}
-        pts = np.asarray(footprint, np.float64).reshape(4, 2)
-        xmin, ymin = pts[:, 0].min(), pts[:, 1].min()
-        xmax, ymax = pts[:, 0].max(), pts[:, 1].max()
-        inv = 1.0 / ele_size                                                        # eleSizeInv
-        x0 = int(math.floor((xmin - mnx) * inv)); y0 = int(math.floor((ymin - mny) * inv))      # .cpp:380-383
-        x1 = int(math.ceil((xmax - mnx) * inv)); y1 = int(math.ceil((ymax - mny) * inv))
-        assert 0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h, "footprint outside the grid it was given"
-        cx, cy = mnx + ele_size * x0, mny + ele_size * y0                           # .cpp:390-391
-        lpi = 1.0 / length_pixel
-        canvas = np.array([[(p[0] - cx) * lpi, (p[1] - cy) * lpi] for p in pts], np.float32)   # Point2f, .cpp:437-438
-        M = np.asarray(M, np.float64).reshape(3, 3)
+        (offx, offy), (x0, y0, x1, y1), canvas, M = canvas_geometry(bgr.shape, grid, footprint, M)
         rows, cols = bgr.shape[:2]
-        corners = np.array([[0, 0], [cols, 0], [0, rows], [cols, rows]], np.float64)
-        proj = (M @ np.c_[corners, np.ones(4)].T).T
-        assert np.abs(proj[:, :2] / proj[:, 2:] - canvas).max() < 1e-3, "M does not map the frame onto its canvas points"
         tx, ty = x1 - x0, y1 - y0
         self.last = ([x0 + offx, y0 + offy, tx, ty], canvas, M)
 
@@ -397,4 +406,154 @@ class ModelMap:
             w0[(iy - y0) * ELE:(iy - y0 + 1) * ELE, (ix - x0) * ELE:(ix - x0 + 1) * ELE] = wts[0]
         out = to_8u(restore_from_laplace_pyr(lv))
         out[w0 == 0] = np.uint8(min(max(self.bg_color, 0), 255))
+        return out, (x0, y0)
+
+
+# ---------------------------------------------------------------- Map2DCPU: one 8-bit band, the weight in the alpha byte
+# Written from Map2DFusion/Map2DCPU.cpp:236-334 and OpenCV 2.4.9's imgwarp.cpp (initInterTab2D, remapBilinear with
+# FixedPtCast<int, uchar, 15>, BORDER_CONSTANT 0); shares no pixel arithmetic with oracle/oracle.c or csrc/single_band.hip.
+def weight_bytes(rows, cols, weight_type):
+    """The alpha plane of weightImage (.cpp:239-258): dis in float; type 0 `dis * 254.` in double, type 1 `dis * dis * 254` in float;
+    the conversion to a byte truncates; then the floor of 2.  ASSUMPTION: `1 - sqrt(dis) / dis_max` is evaluated in float throughout
+    (std::sqrt's float overload, as <cmath> with `using namespace std` picks it).  Were the double sqrt of <math.h> picked instead,
+    the quotient would be rounded once, on the assignment to the float `dis`, and a few bytes could differ.  The oracle and the kernel
+    make the same assumption, so their agreement with this function does not prove the reference's rounding."""
+    xc, yc = F(cols // 2), F(rows // 2)
+    dmax = np.sqrt(xc * xc + yc * yc, dtype=np.float32)
+    i, j = np.mgrid[0:rows, 0:cols].astype(np.float32)
+    d = (i - yc) * (i - yc) + (j - xc) * (j - xc)
+    dis = F(1) - np.sqrt(d, dtype=np.float32) / dmax
+    v = dis.astype(np.float64) * 254.0 if weight_type == 0 else (dis * dis * F(254)).astype(np.float64)
+    return np.maximum(np.trunc(v).astype(np.uint8), np.uint8(2))
+
+
+def linear_tab_fixpt(fixup=True):
+    """initInterTab2D(INTER_LINEAR, fixpt = true): 32 x 32 entries (index fy, fx) of the four taps (1-fy)(1-fx), (1-fy)fx, fy(1-fx),
+    fy fx as float products of the 1-D tables {1.f - x, x}, x = i * (1.f / 32), each saturate_cast<short>(v * 32768).  An entry whose
+    sum is not 32768 gets the difference added to its largest (sum too small) or smallest (too large) element of the window
+    k1, k2 in ksize/2 .. ksize/2 + 1: for the 2 x 2 kernel the only element of the entry in that window is (1, 1)."""
+    x = np.arange(32, dtype=np.float32) * F(1.0 / 32)
+    t1 = np.stack([F(1) - x, x], axis=1)                                          # interpolateLinear
+    tab = np.empty((32, 32, 4), np.int64)
+    for k1 in range(2):
+        for k2 in range(2):
+            v = (t1[:, None, k1] * t1[None, :, k2]) * F(32768)
+            tab[:, :, 2 * k1 + k2] = np.clip(np.rint(v.astype(np.float64)), -32768, 32767).astype(np.int64)
+    if fixup:
+        diff = tab.sum(axis=2) - 32768
+        tab[:, :, 3] -= diff
+        tab[:, :, 3] = tab[:, :, 3].astype(np.int16)                              # the (short) cast of the fix-up
+    return tab
+
+
+_TAB = None
+
+
+def warp_linear_const_8u_inv(src, M, drows, dcols, XY=None):
+    """INTER_LINEAR + BORDER_CONSTANT(0) of an 8-bit image with the inverse map M given: sx = sat_short(X >> 5), the tap entry
+    (Y & 31, X & 31); a pixel with sx >= cols, sx + 1 < 0, sy >= rows or sy + 1 < 0 is the constant; otherwise every tap outside the
+    image reads 0 and the pixel is saturate_cast<uchar>((sum of v * w + (1 << 14)) >> 15), on every channel alike."""
+    global _TAB
+    if _TAB is None:
+        _TAB = linear_tab_fixpt()
+    srows, scols, cn = src.shape
+    X, Y = XY if XY is not None else _warp_coords(M, drows, dcols, (32.0,))[0]
+    sx = np.clip(X >> 5, -32768, 32767); sy = np.clip(Y >> 5, -32768, 32767)
+    w = _TAB[Y & 31, X & 31]
+    s = src.astype(np.int64)
+    acc = np.zeros((drows, dcols, cn), np.int64)
+    for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        px, py = sx + dx, sy + dy
+        ok = (px >= 0) & (px < scols) & (py >= 0) & (py < srows)
+        v = s[np.clip(py, 0, srows - 1), np.clip(px, 0, scols - 1)]
+        acc += np.where(ok[..., None], v, 0) * w[..., k, None]
+    out = np.clip((acc + (1 << 14)) >> 15, 0, 255).astype(np.uint8)
+    out[(sx >= scols) | (sx + 1 < 0) | (sy >= srows) | (sy + 1 < 0)] = 0
+    return out
+
+
+class ModelMapSingleBand:
+    """Map2DCPU (Map2D::create(TypeCPU | TypeGPU)), thread=false, one renderFrame per feed: the frame with the weight byte as its
+    alpha channel is warped onto the canvas, and a stored pixel is replaced where its alpha is SMALLER than the incoming one
+    (.cpp:327) -- among equal alphas the oldest keyframe stays.  Tiles are keyed by world tile like ModelMap's.
+
+    Statistics for the tests: tie_px (pixels where an incoming alpha equalled the stored one, both > 0, summed over the feeds),
+    rim_px (stored pixels with alpha 1: below the floor of 2, so interpolated with the border), and per feed the 64-column x 1-row
+    blocks of the canvas whose pixels all / partly / never have 0 <= sx < cols-1 and 0 <= sy < rows-2 (waves_inside,
+    waves_straddling, waves_outside)."""
+    num_levels = 1
+
+    def __init__(self, weight_type=0):
+        self.weight_type = weight_type
+        self.tiles_ = {}                    # (ix, iy) -> 256 x 256 x 4 uint8 (BGRA)
+        self.grid_ = None
+        self.last = None
+        self._walpha = None
+        self.tie_px = 0
+        self.waves_inside = self.waves_straddling = self.waves_outside = 0
+
+    def freeze(self):
+        """no more feeds: a map that tests share (its statistics are sums over the feeds)"""
+        self.frozen = True
+        return self
+
+    def feed(self, bgr, grid, footprint, M):
+        """The arguments of ModelMap.feed; a fourth channel of the frame is ignored (the map takes the first three)."""
+        assert not getattr(self, "frozen", False), "this model is shared between tests: build another one"
+        self.grid_ = grid
+        (offx, offy), (x0, y0, x1, y1), canvas, M = canvas_geometry(bgr.shape, grid, footprint, M)
+        rows, cols = bgr.shape[:2]
+        tx, ty = x1 - x0, y1 - y0
+        self.last = ([x0 + offx, y0 + offy, tx, ty], canvas, M)
+        if self._walpha is None or self._walpha.shape != (rows, cols):
+            self._walpha = weight_bytes(rows, cols, self.weight_type)
+        src = np.dstack([bgr[:, :, :3], self._walpha])                              # .cpp:266-275
+        crow, ccol = ty * ELE, tx * ELE
+        Minv = invert3x3(M)
+        X, Y = _warp_coords(Minv, crow, ccol, (32.0,))[0]
+        dst = warp_linear_const_8u_inv(src, Minv, crow, ccol, (X, Y))
+        sx = np.clip(X >> 5, -32768, 32767); sy = np.clip(Y >> 5, -32768, 32767)
+        ins = ((sx >= 0) & (sx < cols - 1) & (sy >= 0) & (sy < rows - 2)).reshape(crow, ccol // 64, 64)
+        every, some = ins.all(axis=2), ins.any(axis=2)
+        self.waves_inside += int(every.sum()); self.waves_straddling += int((some & ~every).sum())
+        self.waves_outside += int((~some).sum())
+        tap = [((sx + dx >= 0) & (sx + dx < cols) & (sy + dy >= 0) & (sy + dy < rows)) for dy in (0, 1) for dx in (0, 1)]
+        self.last_dst = dst                                                         # the warped canvas of this feed ...
+        self.last_all_taps = tap[0] & tap[1] & tap[2] & tap[3]                      # ... where all four taps lay inside the frame
+        self.last_no_tap = ~(tap[0] | tap[1] | tap[2] | tap[3])                     # ... and where none did
+        for x in range(x0, x1):                                                     # Apply, .cpp:308-332
+            for y in range(y0, y1):
+                ele = self.tiles_.get((x + offx, y + offy))
+                if ele is None:
+                    ele = self.tiles_[(x + offx, y + offy)] = np.zeros((ELE, ELE, 4), np.uint8)
+                d = dst[(y - y0) * ELE:(y - y0 + 1) * ELE, (x - x0) * ELE:(x - x0 + 1) * ELE]
+                self.tie_px += int(((ele[:, :, 3] == d[:, :, 3]) & (d[:, :, 3] > 0)).sum())
+                sel = ele[:, :, 3] < d[:, :, 3]
+                ele[sel] = d[sel]
+        return True
+
+    @property
+    def rim_px(self):
+        return sum(int((t[:, :, 3] == 1).sum()) for t in self.tiles_.values())
+
+    def tiles(self):
+        return sorted(self.tiles_, key=lambda k: (k[1], k[0]))
+
+    def tile_bgra(self, ix, iy):
+        t = self.tiles_.get((ix, iy))
+        return None if t is None else t.copy()
+
+    def blend_tile(self, ix, iy):
+        t = self.tiles_.get((ix, iy))
+        return None if t is None else t[:, :, :3].copy()
+
+    def save(self):
+        """The tiles' BGR pasted over their bounding box, holes zero.  Returns (image, (tile x0, tile y0)) like ModelMap.save."""
+        if not self.tiles_:
+            return None
+        xs = [k[0] for k in self.tiles_]; ys = [k[1] for k in self.tiles_]
+        x0, y0 = min(xs), min(ys)
+        out = np.zeros(((max(ys) + 1 - y0) * ELE, (max(xs) + 1 - x0) * ELE, 3), np.uint8)
+        for (ix, iy), t in self.tiles_.items():
+            out[(iy - y0) * ELE:(iy - y0 + 1) * ELE, (ix - x0) * ELE:(ix - x0 + 1) * ELE] = t[:, :, :3]
         return out, (x0, y0)

@@ -70,6 +70,35 @@ def test_cfg2_timed_path_two_flight_lines_against_oracle(pf, orc, force_float):
     g.close()
 
 
+def test_cfg2_single_band_two_flight_lines_against_oracle(pf, orc):
+    """The single-band map (TypeCPU: k_single2) at the size bench.py times it at: fourteen device-resident 4000x3000 keyframes over two
+    flight lines of cfg-2's camera, the default lookahead and the cull; every tile_bgra and the saved mosaic against the oracle."""
+    torch = pytest.importorskip("torch")
+    wl = workloads()
+    cam = [4000, 3000, 3000, 3000, 2000, 1500]
+    poses = wl.serpentine(cam, 100.0, 14, per_row=7)
+    host = [wl.noise_frame(3000, 4000, 90), wl.smooth_frame(3000, 4000, 5), wl.noise_frame(3000, 4000, 91)]
+    dev = [torch.from_numpy(f).cuda() for f in host]
+    g = pf.Map2D.create(pf.TypeCPU, False)
+    o = orc.OracleMap(single_band=1)
+    assert g.prepare(wl.IDENTITY_PLANE, cam, poses) and o.prepare(wl.IDENTITY_PLANE, cam, poses)
+    for k, p in enumerate(poses):
+        assert g.feed_device(dev[k % 3].data_ptr(), 3000, 4000, p) and o.feed(host[k % 3], p)
+    assert g.sync() and g.grid() == o.grid()
+    tiles = o.tiles()
+    assert g.tiles() == tiles and len(tiles) > 300
+    bad = [t for t in tiles if not np.array_equal(g.tile_bgra(*t), o.tile_bgra(*t))]
+    assert bad == [], bad[:6]
+    assert g.culled_tiles() + g.culled_cells() > 0
+    img, (x0, y0) = g.save_to_memory()
+    assert (x0, y0) == (min(t[0] for t in tiles), min(t[1] for t in tiles))
+    exp = np.zeros_like(img)
+    for (ix, iy) in tiles:
+        exp[(iy - y0) * 256:(iy - y0 + 1) * 256, (ix - x0) * 256:(ix - x0 + 1) * 256] = o.tile_bgra(ix, iy)[:, :, :3]
+    assert np.array_equal(img, exp)
+    g.close()
+
+
 def test_cfg4_65536_tile_store_and_7band_frames(pf, orc):
     torch = pytest.importorskip("torch")
     free, _ = torch.cuda.mem_get_info()

@@ -138,7 +138,8 @@ def test_hostile_frames_hip_equals_model_and_oracle(pf, kind, force_float, bands
 
 @pytest.mark.parametrize("kind", HOSTILE_KINDS)
 def test_single_band_hostile_frames(pf, orc, kind):
-    """Map2DCPU (TypeCPU) on the same frames against the oracle, through tile_bgra (the model covers the multi-band map only)."""
+    """Map2DCPU (TypeCPU) on the same frames against the oracle, through tile_bgra (the single-band map has its own model,
+    ModelMapSingleBand, and its own three-witness cases: test_gpu_single_band_model.py)."""
     wl = workloads()
     poses = jitter_poses(N, seed=29, step=(30.0, 20.0))
     g = pf.Map2D.create(pf.TypeCPU, False)

@@ -109,8 +109,9 @@ def test_single_band_shards(pf):
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", ["PF_SINGLE_OLD", "PF_FORCE_GENERAL"])
 def test_single_band_other_kernel_forms(env):
-    """The one-pixel-per-thread kernel and the general coordinate/tap forms of k_single2 give the same tiles; both
-    are selected by environment switches that are read once per process, hence the child process."""
+    """The one-pixel-per-thread kernel and the general coordinate/tap forms of k_single2 give the same tiles, on noise and on the
+    hostile frames (saturated, flat, pixel-sharp) with both weight types; both are selected by environment switches that are read
+    once per process, hence the child process."""
     import os, subprocess, sys
     here = os.path.dirname(os.path.abspath(__file__))
     code = (
@@ -121,10 +122,15 @@ def test_single_band_other_kernel_forms(env):
         "import test_single_band as T\n"
         "pf = load_package(); from oracle import orc\n"
         "wl = workloads(); cam = [640, 480, 500, 500, 320, 240]\n"
-        "poses = jitter_poses(5, seed=23); frames = [wl.noise_frame(480, 640, 60 + k) for k in range(5)]\n"
-        "g, o = T.run_pair(pf, orc, cam, poses, frames, pf.TypeCPU, n_prepare=2)\n"
-        "for t in o.tiles():\n"
-        "    assert np.array_equal(g.tile_bgra(*t), o.tile_bgra(*t)), t\n"
+        "from helpers import HOSTILE_KINDS, hostile_frame\n"
+        "poses = jitter_poses(5, seed=23)\n"
+        "for kind in HOSTILE_KINDS:\n"
+        "    for wt in (0, 1):\n"
+        "        frames = [wl.noise_frame(480, 640, 60 + k) if kind == 'noise' else hostile_frame(kind, 480, 640, k) for k in range(5)]\n"
+        "        g, o = T.run_pair(pf, orc, cam, poses, frames, pf.TypeCPU, n_prepare=2, weight_type=wt)\n"
+        "        for t in o.tiles():\n"
+        "            assert np.array_equal(g.tile_bgra(*t), o.tile_bgra(*t)), (kind, wt, t)\n"
+        "        g.close()\n"
         "print('single band ok')\n"
     ) % (here, os.path.dirname(here))
     exp = os.path.join(os.path.dirname(here), "pi-slam-fusion_amd", "libpifusion_exp.so")      # the switches exist in the experiments build only (csrc/env.hpp)
