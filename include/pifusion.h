@@ -119,12 +119,51 @@ int     pf_sync(pf_map* m);
  * JPEG (.jpg / .jpeg, either case: quality 95, 4:2:0, cv::imwrite's default;
  * the collapsed mosaic is encoded on the GPU and only the stream comes back;
  * a mosaic of more than 65535 pixels a side returns 0 and writes no file),
+ * a tiled pyramid TIFF (.tif / .tiff, either case: pf_save_tiff at quality
+ * 95, classic unless the file needs BigTIFF; no limit on the mosaic's side),
  * else binary PPM.                                                         */
 int     pf_save(pf_map* m, const char* filename);
+/* save("x.tif") with what pf_save cannot carry: the tiles' JPEG quality and a flag that forces BigTIFF.  The file is
+ * pf_tiff_write_bgr(filename, <the mosaic pf_save_to_memory returns>, quality, Result.BackGroundColor, T, force_bigtiff) with
+ * T = the affine pixel (column, row) -> plane coordinates in metres: x = min.x + (tile_x0 - off_x) * eleSize + column *
+ * lengthPixel, y = min.y + (tile_y0 - off_y) * eleSize + row * lengthPixel (pf_grid's geo and dims, pf_save_to_memory's origin
+ * tile; row-major 4 x 4, z = 0).  Multi-band maps: overview chain, empty test and tile encode run on the GPU on the mosaic where the
+ * collapse left it (csrc/overview.hip, jpeg_encode.hip); only flags, offsets and streams cross to the host.  Any file name.  */
+int     pf_save_tiff(pf_map* m, const char* filename, int quality, int force_bigtiff);
 /* The file leg of save() alone: cv::imwrite(filename, result), MultiBandMap2DCPU.cpp:841.  8-bit BGR in,
  * PNG (8-bit RGB, deflate) when the name ends in .png/.PNG, JPEG (pf_jpeg_encode_bgr at quality 95) when it ends in
- * .jpg/.jpeg in either case, binary PPM (P6) otherwise.  No device needed. */
+ * .jpg/.jpeg in either case, the pyramid TIFF (pf_tiff_write_bgr at quality 95, background 0, no geo tags) when it ends in
+ * .tif/.tiff in either case, binary PPM (P6) otherwise.  No device needed. */
 int     pf_write_image(const char* filename, const uint8_t* bgr, int rows, int cols);
+/* The tiled pyramid TIFF of an orthomosaic (no reference counterpart: the reference writes one big .jpg / .png).  One
+ * little-endian file, a pure function of (pixels, quality, bg, model_transform, force_bigtiff):
+ *   images   image 0 = the rows x cols BGR picture (any size >= 1, `step` bytes per row, 0 = packed); image k >= 1 = the 2 x 2
+ *            mean of image k - 1: ceil(r/2) x ceil(c/2), every channel (p00 + p01 + p10 + p11 + 2) >> 2, a missing last row or
+ *            column repeating the one before it; the chain ends with the first image of at most 256 x 256.  NewSubfileType 0
+ *            for image 0, 1 (reduced resolution) for the others; IFDs chained in that order.
+ *   tiles    256 x 256, row-major; past the image its last column, then its last row, repeated.  Every tile is a complete
+ *            baseline JPEG stream, the bytes of pf_jpeg_encode_bgr(tile, 256, 256, 0, quality): Compression 7, Photometric 6
+ *            (YCbCr), YCbCrSubSampling 2 2, BitsPerSample 8 8 8, SamplesPerPixel 3, PlanarConfiguration 1, no JPEGTables.
+ *   empty    a tile whose 256 x 256 filled pixels all equal the background colour (bg saturated to 8 bits, in all channels) is
+ *            stored once: every such tile of every image has the same TileOffsets and TileByteCounts value.
+ *   geo      model_transform != NULL: image 0 carries ModelTransformationTag (34264, the 16 doubles, row-major 4 x 4: pixel
+ *            (column, row, 0, 1) -> model coordinates) and a GeoKeyDirectoryTag (34735) that says user-defined model type
+ *            (1024 = 32767) and RasterPixelIsArea (1025 = 1), no CRS.
+ *   layout   header; then per image, in order: its IFD (tags sorted), followed by the values that do not fit an entry, in tag
+ *            order (BitsPerSample, TileOffsets, TileByteCounts, the doubles, the GeoKeys); then the empty tile's stream, if any
+ *            tile is empty; then the streams of the other tiles, image by image, row-major.  Every IFD, value and stream starts
+ *            on an even offset.  Classic TIFF (42, 32-bit offsets) when the file ends below 4 GiB, BigTIFF (43, 64-bit offsets,
+ *            TileOffsets as LONG8) otherwise or when force_bigtiff is set.  (csrc/tiff_pyramid.hpp, tiff::layout: the one
+ *            function both this writer and the GPU path place bytes by.)
+ * Host code, no device.  0 + pf_last_error() on failure, and no file is left behind.                                        */
+int     pf_tiff_write_bgr(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg,
+                          const double model_transform[16], int force_bigtiff);
+/* The same file, byte for byte, from an image of any size in device memory: the overview chain (csrc/overview.hip: each group of
+ * three levels from one read of the level above), the empty test and the tile encode (csrc/jpeg_encode.hip, in bounded batches,
+ * empty tiles skipped) run on the GPU in the order of `hip_stream` (a hipStream_t, NULL = the default stream); flags, offsets
+ * and streams cross to the host, pixels do not.  The counterpart of pf_jpeg_encode_device; returns when the file is written. */
+int     pf_tiff_write_device(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, int quality, int bg,
+                             const double model_transform[16], int force_bigtiff, void* hip_stream);
 /* cv::imencode(".jpg") / the JPEG leg of cv::imwrite of OpenCV 2.4.9: baseline JPEG, byte for byte what libjpeg writes after
  * jpeg_set_defaults, JCS_RGB input and jpeg_set_quality(quality, TRUE) -- JFIF 1.01, 4:2:0, the Annex K tables, one interleaved
  * scan, integer colour conversion and ISLOW DCT.  bgr: rows x cols 8-bit BGR, `step` bytes per row (0 = packed).  quality is

@@ -154,7 +154,9 @@ public:
     }
     // svar "Fuse2Google" and "GPS.Origin" (longitude latitude altitude) of the reference (.cpp:196, :744)
     void fuseGoogle(bool on, double lng = 0, double lat = 0, double alt = 0) { fuse2google_ = on; gps_origin_[0] = lng; gps_origin_[1] = lat; gps_origin_[2] = alt; }
+    // .png, .jpg / .jpeg, .tif / .tiff (tiled pyramid TIFF with JPEG tiles, overviews and geo tags), else PPM: see pf_save
     bool save(const std::string& filename) { return pf_save(h_, filename.c_str()) != 0; }
+    bool saveTiff(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
     unsigned queueSize() { return pf_queue_size(h_); }
     bool sync() { return pf_sync(h_) != 0; }
 

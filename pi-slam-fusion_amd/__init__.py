@@ -108,6 +108,10 @@ def lib():
         L.pf_jpeg_encode_bgr.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.pf_jpeg_encode_device.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
         L.pf_blend_tiles_jpeg.argtypes = [vp, ip, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "pf_tiff_write_bgr") or not os.environ.get("PF_LIB"):
+        L.pf_tiff_write_bgr.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, dp, C.c_int]
+        L.pf_tiff_write_device.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, dp, C.c_int, vp]
+        L.pf_save_tiff.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
     L.pf_debug_jpeg_huffman.argtypes = [vp, C.POINTER(C.c_longlong)]; L.pf_debug_jpeg_huffman.restype = None
     L.pf_feed_jpeg_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), dp, C.c_int, ip]
     L.pf_num_levels.argtypes = [vp]
@@ -310,6 +314,31 @@ def jpeg_encode_device(dev_ptr, rows, cols, quality=95, step=0, stream=None):
     return out[:n.value].tobytes()
 
 
+def _transform16(model_transform):
+    if model_transform is None:
+        return None, None
+    a = np.ascontiguousarray(model_transform, dtype=np.float64).reshape(16)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def tiff_write(filename, bgr, quality=95, bg=0, model_transform=None, force_bigtiff=False):
+    """HxWx3 BGR uint8 (rows may be padded) -> the tiled pyramid TIFF of pf_tiff_write_bgr (include/pifusion.h): JPEG tiles of 256 x 256,
+    2 x 2-mean overviews down to one tile, all-background tiles stored once, geo tags when the 16 doubles are given.  Host code."""
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(bgr, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("tiff_write: HxWx3 expected")
+    keep, xf = _transform16(model_transform)
+    return bool(lib().pf_tiff_write_bgr(filename.encode(), a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], quality, bg, xf, int(force_bigtiff)))
+
+
+def tiff_write_device(filename, dev_ptr, rows, cols, quality=95, bg=0, model_transform=None, force_bigtiff=False, step=0, stream=None):
+    """The same file, byte for byte, from rows x cols BGR8 pixels at the device address `dev_ptr` (csrc/overview.hip + jpeg_encode.hip)."""
+    keep, xf = _transform16(model_transform)
+    return bool(lib().pf_tiff_write_device(filename.encode(), dev_ptr, rows, cols, step, quality, bg, xf, int(force_bigtiff), stream))
+
+
 def jpeg_huffman_counts(map2d=None):
     """(frames whose Huffman pass ran on the GPU, frames that fell back to the host after trying, rounds of the most recent GPU pass) of a map's
     decoder, or of decode_jpeg_device's when map2d is None"""
@@ -426,6 +455,10 @@ class Map2D:
 
     def save(self, filename):
         return bool(lib().pf_save(self._h, filename.encode()))
+
+    def save_tiff(self, filename, quality=95, force_bigtiff=False):
+        """save("x.tif") with the tiles' JPEG quality and the flag that forces BigTIFF (pf_save_tiff)"""
+        return bool(lib().pf_save_tiff(self._h, filename.encode(), quality, int(force_bigtiff)))
 
     def save_to_memory(self, alloc=None):
         """(mosaic BGR8, (tile x0, tile y0)); alloc(shape) -> uint8 array supplies the buffer (e.g. host_array)."""

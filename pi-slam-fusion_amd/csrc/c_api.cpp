@@ -91,6 +91,7 @@ long pf_debug_read_last_frame(pf_map* m, void* out, size_t cap) { return m ? m->
 unsigned pf_queue_size(pf_map* m) { return m ? m->impl.queue_size() : 0; }
 int pf_sync(pf_map* m) { return m && m->impl.sync(); }
 int pf_save(pf_map* m, const char* filename) { return m && filename && m->impl.save(filename); }
+int pf_save_tiff(pf_map* m, const char* filename, int quality, int force_bigtiff) { return m && filename && m->impl.save_tiff(filename, quality, force_bigtiff != 0); }
 // pf_write_image / pf_image_info / pf_read_image: image_io.cpp (host code without a HIP dependency: also built by the sanitizer targets)
 int pf_jpeg_info(const uint8_t* data, size_t len, int* rows, int* cols, int* components) { return pf::jpeg_info(data, len, rows, cols, components); }
 int pf_jpeg_decode_bgr(const uint8_t* data, size_t len, uint8_t* bgr, int rows, int cols)
@@ -141,6 +142,29 @@ int pf_jpeg_encode_device(const void* dev_bgr, int rows, int cols, size_t step, 
             ok = 0;
         } else ok = e->fetch(out, hip_stream);
     }
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
+// pf_tiff_write_device's level buffers: one set per device, beside the encoder
+static pf::TiffDevice* shared_tiff_device(int device)
+{
+    static pf::TiffDevice* t[64] = {};
+    if (device < 0 || device >= 64) device = 0;
+    if (!t[device]) t[device] = new pf::TiffDevice();
+    return t[device];
+}
+int pf_tiff_write_device(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, int quality, int bg, const double model_transform[16], int force_bigtiff, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_jpeg_mu);
+    if (!filename || !dev_bgr || rows <= 0 || cols <= 0) { pf::set_error("pf_tiff_write_device: no name, no image or a size that is not positive"); return 0; }
+    if (step == 0) step = (size_t)cols * 3;
+    if (step < (size_t)cols * 3) { pf::set_error("pf_tiff_write_device: step is smaller than a row"); return 0; }
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dev_bgr) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_tiff_write_device: the image is not in device memory"); return 0; }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_tiff_write_device: hipSetDevice failed"); return 0; }
+    const int ok = shared_tiff_device(at.device)->write(filename, dev_bgr, rows, cols, step, quality, bg, model_transform, force_bigtiff != 0, *shared_jpeg_encoder(at.device), hip_stream);
     if (at.device != prev) (void)hipSetDevice(prev);
     return ok;
 }

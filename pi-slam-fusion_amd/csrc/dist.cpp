@@ -475,7 +475,17 @@ bool DistMap::save(const char* filename)
 {
     int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
     if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
-    if (is_jpeg_name(filename) && !m_->single_band()) {          // rank 0 encodes the gathered mosaic on its GPU (every rank takes this branch: the exchange is collective)
+    if (is_tiff_name(filename) && m_->single_band()) {          // gathered as pixels, written by the host writer with the map's geo tags
+        std::vector<uint8_t> img((size_t)rows * cols * 3 + 1);
+        if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
+        if (t_->rank != 0) return true;
+        double xf[16];
+        m_->tiff_transform(tx0, ty0, xf);
+        if (!write_tiff_file("save", filename, img.data(), rows, cols, 0, 95, m_->bg_color(), xf, false)) return false;
+        std::printf("Resolution:[%d %d]\n", cols, rows);
+        return true;
+    }
+    if ((is_jpeg_name(filename) || is_tiff_name(filename)) && !m_->single_band()) {          // rank 0 encodes the gathered mosaic on its GPU (every rank takes this branch: the exchange is collective)
         if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0, filename)) return false;          // rank 0's map writes the file
         if (t_->rank != 0) return true;
         std::printf("Resolution:[%d %d]\n", cols, rows);

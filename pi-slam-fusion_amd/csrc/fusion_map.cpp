@@ -231,7 +231,7 @@ FusionMap::~FusionMap()
     if (out_ready_) (void)hipEventDestroy(out_ready_);
     if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
     blend_src_.release(); blend_out_raw_.release(); blend_out_bgr_.release(); mosaic_table_.release(); w8_.release(); wmap_.release();
-    jpeg_enc_.release();
+    jpeg_enc_.release(); tiff_dev_.release();
     store_.clear();
     (void)hipStreamDestroy(stream_);
 }
@@ -2299,7 +2299,11 @@ bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int
     *rows = wy * kElePixels; *cols = wx * kElePixels; *tx0 = mnx; *ty0 = mny;
     if (!bgr && !jpeg) return true;
     if (jpeg && (bgr || single_band_)) { set_error("save: the stream of a mosaic in HBM was asked for where there is none"); return false; }
-    if (jpeg && !jpeg_size_ok("save", *rows, *cols)) return false;
+    const bool tiff = jpeg && (tiff_forced_ || is_tiff_name(jpeg));
+    const int tiff_q = tiff_forced_ ? tiff_quality_ : 95;
+    const bool tiff_big = tiff_forced_ && tiff_big_;
+    tiff_forced_ = false;
+    if (jpeg && !tiff && !jpeg_size_ok("save", *rows, *cols)) return false;
     if (single_band_) {          // Map2DCPU::save (Map2DCPU.cpp:523-563): paste the tiles; holes are zero here
         HIP_OK(sync_all());
         std::memset(bgr, 0, (size_t)*rows * *cols * 3);
@@ -2356,6 +2360,11 @@ bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int
     launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
     prof_end();
     HIP_OK(hipGetLastError());
+    if (tiff) {          // the mosaic stays where the collapse left it: overviews, empty test and tile streams are made from it there
+        double xf[16];
+        tiff_transform_locked(*tx0, *ty0, xf);
+        return tiff_dev_.write(jpeg, blend_out_bgr_.p, *rows, *cols, (size_t)*cols * 3, tiff_q, opt_.bg_color, xf, tiff_big, jpeg_enc_, stream_);
+    }
     if (jpeg) {          // the mosaic stays where the collapse left it; cv::imwrite's JPEG defaults: quality 95, 4:2:0
         size_t off[2];
         if (!jpeg_enc_.encode(blend_out_bgr_.p, 1, nullptr, 0, *rows, *cols, (size_t)*cols * 3, 95, off, stream_)) return false;
@@ -2366,9 +2375,41 @@ bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int
     return true;
 }
 
+void FusionMap::tiff_transform_locked(int tx0, int ty0, double out[16])
+{
+    for (int i = 0; i < 16; i++) out[i] = 0;
+    out[0] = length_pixel_; out[3] = min_[0] + (tx0 - off_x_) * ele_size_;
+    out[5] = length_pixel_; out[7] = min_[1] + (ty0 - off_y_) * ele_size_;
+    out[10] = 1; out[15] = 1;
+}
+void FusionMap::tiff_transform(int tx0, int ty0, double out[16])
+{
+    std::lock_guard<std::mutex> l(mu_);
+    tiff_transform_locked(tx0, ty0, out);
+}
+
+bool FusionMap::save_tiff(const char* filename, int quality, bool force_bigtiff)
+{
+    int rows, cols, tx0, ty0;
+    if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
+    if (!single_band_) {          // multi-band: made on the GPU from the mosaic in HBM
+        set_tiff_options(quality, force_bigtiff);
+        if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0, nullptr, filename)) { tiff_forced_ = false; return false; }
+    } else {
+        std::vector<uint8_t> img((size_t)rows * cols * 3);
+        if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
+        double xf[16];
+        tiff_transform(tx0, ty0, xf);
+        if (!write_tiff_file("save", filename, img.data(), rows, cols, 0, quality, opt_.bg_color, xf, force_bigtiff)) return false;
+    }
+    std::printf("Resolution:[%d %d]\n", cols, rows);
+    return true;
+}
+
 bool FusionMap::save(const char* filename)
 {
     int rows, cols, tx0, ty0;
+    if (is_tiff_name(filename)) return save_tiff(filename, 95, false);
     if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
     if (is_jpeg_name(filename) && !single_band_) {          // multi-band: encoded on the GPU, only the stream is copied and written
         if (!jpeg_size_ok("save", rows, cols)) return false;

@@ -7,6 +7,7 @@
 #include "dist_plan.hpp"
 #include "env.hpp"
 #include "jpeg_encode.hpp"
+#include "tiff_pyramid.hpp"
 #include <hip/hip_runtime.h>
 #include <condition_variable>
 #include <cstdlib>
@@ -106,9 +107,17 @@ public:
     long read_back_last_frame(void* out, size_t cap);
     bool sync();
     bool save(const char* filename);
+    // save("x.tif") with the tiles' JPEG quality and the flag that forces BigTIFF (pf_save_tiff); any file name
+    bool save_tiff(const char* filename, int quality, bool force_bigtiff);
+    // what the next save_to_memory(.., a .tif name) encodes with (DistMap::save sets them as save() does)
+    void set_tiff_options(int quality, bool force_bigtiff) { tiff_quality_ = quality; tiff_big_ = force_bigtiff; tiff_forced_ = true; }
+    // the 16 doubles of the file's ModelTransformationTag for a mosaic whose origin tile is (tx0, ty0)
+    void tiff_transform(int tx0, int ty0, double out[16]);
+    int  bg_color() const { return opt_.bg_color; }
     struct ForeignTile { int ix, iy; const void* dev; };          // a tile slot image held outside the store (gathered for save)
     // jpeg_file (bgr == nullptr): the collapsed mosaic stays in HBM and leaves as the JPEG stream save("x.jpg") writes
-    // (jpeg_encode.hip), which lands in the encoder's page-locked buffer and goes to that file
+    // (jpeg_encode.hip), which lands in the encoder's page-locked buffer and goes to that file; a name that ends in .tif / .tiff
+    // (or any name after set_tiff_options): the pyramid TIFF of overview.hip instead, from the same mosaic in HBM
     bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const std::vector<ForeignTile>* foreign = nullptr, const char* jpeg_file = nullptr);
 
     // seam exchange support (dist.cpp)
@@ -359,6 +368,9 @@ private:
     DevBuf blend_lv_[kMaxLevels], blend_src_, blend_out_raw_, blend_out_bgr_, mosaic_table_, strip_desc_;
     // results on their way to the host: two pinned staging slots, filled on copy_stream_ while the host empties the other one
     static constexpr size_t kOutSlot = (size_t)32 << 20;
+    void tiff_transform_locked(int tx0, int ty0, double out[16]);
+    TiffDevice  tiff_dev_;      // save("x.tif"): level buffers and flags of its own, tiles through jpeg_enc_
+    int  tiff_quality_ = 95; bool tiff_big_ = false, tiff_forced_ = false;
     JpegEncoder jpeg_enc_;      // save("x.jpg"), pf_blend_tiles_jpeg: reads blend_out_bgr_ on stream_, buffers of its own
     struct OutPiece { void* dst; const void* src; size_t bytes; };      // host destination, device source
     uint8_t*    out_pin_[2]{};
@@ -404,6 +416,8 @@ private:
 // PNG (zlib) / PPM writer for save()
 bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int cols);
 bool is_jpeg_name(const char* filename);                                      // image_io.cpp
+bool is_tiff_name(const char* filename);
+bool write_tiff_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff);
 bool jpeg_size_ok(const char* who, int rows, int cols);
 bool write_bytes_file(const char* filename, const uint8_t* data, size_t len);
 

@@ -1,10 +1,12 @@
 // image_io.cpp -- output side of save(): the reference hands the mosaic to
 // cv::imwrite (MultiBandMap2DCPU.cpp:841).  PNG (8-bit RGB, zlib stream split
 // over IDAT chunks) when the name ends in .png, JPEG (quality 95, 4:2:0: cv::imwrite's
-// default, jpeg_encode.hpp) when it ends in .jpg / .jpeg, binary PPM otherwise.
+// default, jpeg_encode.hpp) when it ends in .jpg / .jpeg, a tiled pyramid TIFF with JPEG tiles
+// (tiff_pyramid.hpp) when it ends in .tif / .tiff, binary PPM otherwise.
 #include "../../include/pifusion.h"
 #include "jpeg_decode.hpp"
 #include "jpeg_encode.hpp"
+#include "tiff_pyramid.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -122,17 +124,25 @@ static bool write_png(FILE* f, const uint8_t* bgr, int rows, int cols)
     return ok && png_chunk(f, "IEND", nullptr, 0);
 }
 
-// the name ends in .jpg / .jpeg, in either case: cv::imwrite hands the image to its JPEG encoder
-bool is_jpeg_name(const char* filename)
+static bool name_ends(const char* filename, const char* ext)
 {
-    const size_t n = std::strlen(filename);
-    auto ends = [&](const char* ext) {
-        const size_t k = std::strlen(ext);
-        if (n < k) return false;
-        for (size_t i = 0; i < k; i++) { char c = filename[n - k + i]; if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a'); if (c != ext[i]) return false; }
-        return true;
-    };
-    return ends(".jpg") || ends(".jpeg");
+    const size_t n = std::strlen(filename), k = std::strlen(ext);
+    if (n < k) return false;
+    for (size_t i = 0; i < k; i++) { char c = filename[n - k + i]; if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a'); if (c != ext[i]) return false; }
+    return true;
+}
+// the name ends in .jpg / .jpeg, in either case: cv::imwrite hands the image to its JPEG encoder
+bool is_jpeg_name(const char* filename) { return name_ends(filename, ".jpg") || name_ends(filename, ".jpeg"); }
+// ... in .tif / .tiff, in either case: the tiled pyramid TIFF (no reference counterpart: the reference writes none)
+bool is_tiff_name(const char* filename) { return name_ends(filename, ".tif") || name_ends(filename, ".tiff"); }
+
+bool write_tiff_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff)
+{
+    if (!filename || !bgr || rows <= 0 || cols <= 0) { set_error(std::string(who) + ": no name, no image or a size that is not positive"); return false; }
+    if (step == 0) step = (size_t)cols * 3;
+    if (step < (size_t)cols * 3) { set_error(std::string(who) + ": step is smaller than a row"); return false; }
+    try { return tiff::write_bgr(filename, bgr, rows, cols, step, quality, bg, model_transform, force_bigtiff); }
+    catch (const std::bad_alloc&) { std::remove(filename); set_error(std::string(who) + ": out of memory"); return false; }
 }
 
 bool jpeg_size_ok(const char* who, int rows, int cols)
@@ -159,6 +169,7 @@ bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int co
         try { jenc::encode_bgr(bgr, rows, cols, (size_t)cols * 3, 95, stream); } catch (const std::bad_alloc&) { set_error("save: out of memory"); return false; }
         return write_bytes_file(filename, stream.data(), stream.size());
     }
+    if (is_tiff_name(filename)) return write_tiff_file("save", filename, bgr, rows, cols, 0, 95, 0, nullptr, false);
     FILE* f = std::fopen(filename, "wb");
     if (!f) { set_error(std::string("save: cannot open ") + filename); return false; }
     const size_t n = std::strlen(filename);
@@ -199,6 +210,8 @@ int pf_jpeg_encode_bgr(const uint8_t* bgr, int rows, int cols, size_t step, int 
     std::memcpy(out, stream.data(), stream.size());
     return 1;
 }
+int pf_tiff_write_bgr(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double model_transform[16], int force_bigtiff)
+{ return pf::write_tiff_file("pf_tiff_write_bgr", filename, bgr, rows, cols, step, quality, bg, model_transform, force_bigtiff != 0); }
 int pf_image_info(const char* filename, int* rows, int* cols)
 {
     if (!filename || !rows || !cols) return 0;

@@ -41,7 +41,7 @@ __device__ inline McuPos mcu_pos(long mcu, long n_mcus, const Geometry& g)
     return p;
 }
 
-__global__ __launch_bounds__(kTransformLanes) void k_jenc_transform(const uint8_t* __restrict__ src, const int* __restrict__ slots, size_t image_stride,
+__global__ __launch_bounds__(kTransformLanes) void k_jenc_transform(const uint8_t* __restrict__ src, const long long* __restrict__ where, size_t image_stride,
                                                                     size_t step, Geometry g, long n_mcus, const EncBlob* __restrict__ blob,
                                                                     int16_t* __restrict__ coef, int16_t* __restrict__ dcv, uint32_t* __restrict__ acbits)
 {
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(kTransformLanes) void k_jenc_transform(const uint8_
         const int ml = t / 48, j = t - 48 * ml;
         const McuPos p = mcu_pos(mcu0 + ml, n_mcus, g);
         if (p.valid) {
-            const uint8_t* base = src + (size_t)(slots ? slots[p.img] : p.img) * image_stride;
+            const uint8_t* base = src + (where ? (size_t)where[p.img] : (size_t)p.img * image_stride);          // where: byte offsets, 64 bits
             const int x = min(16 * p.mx + j / 3, g.cols - 1);
             for (int r = 0; r < 16; r++) {
                 const int y = min(16 * p.my + r, g.rows - 1);
@@ -330,6 +330,15 @@ JpegEncoder::~JpegEncoder() { delete p_; }
 void JpegEncoder::release() { delete p_; p_ = nullptr; }
 
 bool JpegEncoder::encode(const void* dev_bgr, int n, const int* slots, size_t image_stride, int rows, int cols, size_t step, int quality, size_t* offsets, void* stream)
+{ return encode_at(dev_bgr, n, slots, nullptr, image_stride, rows, cols, step, quality, offsets, stream); }
+
+bool JpegEncoder::encode_windows(const void* dev_base, int n, const long long* byte_offsets, int rows, int cols, size_t step, int quality, size_t* offsets, void* stream)
+{
+    if (!byte_offsets) { set_error("jpeg encoder: bad arguments"); return false; }
+    return encode_at(dev_base, n, nullptr, byte_offsets, 0, rows, cols, step, quality, offsets, stream);
+}
+
+bool JpegEncoder::encode_at(const void* dev_bgr, int n, const int* slots, const long long* where, size_t image_stride, int rows, int cols, size_t step, int quality, size_t* offsets, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;
     if (!dev_bgr || n < 1 || rows < 1 || cols < 1 || rows > kMaxDim || cols > kMaxDim || step < (size_t)cols * 3 || !offsets) { set_error("jpeg encoder: bad arguments"); return false; }
@@ -351,18 +360,19 @@ bool JpegEncoder::encode(const void* dev_bgr, int n, const int* slots, size_t im
         d.quality = quality; d.rows = rows; d.cols = cols;
     }
     const EncBlob* blob = (const EncBlob*)d.blob.p;
-    int* dslots = nullptr;
+    long long* dwhere = nullptr;
+    const bool listed = slots || where;
     if (!d.coef.reserve((size_t)nb * 128) || !d.dcv.reserve((size_t)nb * 2) || !d.acbits.reserve((size_t)nb * 4) || !d.bits.reserve((size_t)(nb + 1) * 8) ||
-        !d.off.reserve((size_t)(nb + 1) * 8) || !d.chunks.reserve((size_t)(n + 1) * 8 + (slots ? (size_t)n * 4 : 0)) || !d.ubase.reserve((size_t)(n + 1) * 8) ||
-        !d.flen.reserve((size_t)(n + 1) * 8) || !d.fbase.reserve((size_t)(n + 1) * 8) || !d.pin((size_t)(n + 2) * 8 + (slots ? (size_t)n * 4 : 0))) return false;
-    if (slots) {          // through the pinned buffer: the caller's list may go away before the copy runs
-        int* hs = (int*)((char*)d.pinned + (size_t)(n + 2) * 8);
-        std::memcpy(hs, slots, (size_t)n * 4);
-        dslots = (int*)((char*)d.chunks.p + (size_t)(n + 1) * 8);
-        JENC_OK(hipMemcpyAsync(dslots, hs, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        !d.off.reserve((size_t)(nb + 1) * 8) || !d.chunks.reserve((size_t)(n + 1) * 8 + (listed ? (size_t)n * 8 : 0)) || !d.ubase.reserve((size_t)(n + 1) * 8) ||
+        !d.flen.reserve((size_t)(n + 1) * 8) || !d.fbase.reserve((size_t)(n + 1) * 8) || !d.pin((size_t)(n + 2) * 8 + (listed ? (size_t)n * 8 : 0))) return false;
+    if (listed) {          // as byte offsets, through the pinned buffer: the caller's list may go away before the copy runs
+        long long* hs = (long long*)((char*)d.pinned + (size_t)(n + 2) * 8);
+        for (int i = 0; i < n; i++) hs[i] = where ? where[i] : (long long)slots[i] * (long long)image_stride;
+        dwhere = (long long*)((char*)d.chunks.p + (size_t)(n + 1) * 8);
+        JENC_OK(hipMemcpyAsync(dwhere, hs, (size_t)n * 8, hipMemcpyHostToDevice, s));
     }
     const unsigned per_img = (unsigned)((n + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_jenc_transform, dim3((unsigned)((n_mcus + kGroupMcus - 1) / kGroupMcus)), dim3(kTransformLanes), 0, s, (const uint8_t*)dev_bgr, dslots, image_stride, step, g,
+    hipLaunchKernelGGL(k_jenc_transform, dim3((unsigned)((n_mcus + kGroupMcus - 1) / kGroupMcus)), dim3(kTransformLanes), 0, s, (const uint8_t*)dev_bgr, dwhere, image_stride, step, g,
                        n_mcus, blob, (int16_t*)d.coef.p, (int16_t*)d.dcv.p, (uint32_t*)d.acbits.p);
     hipLaunchKernelGGL(k_jenc_bits, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, (const int16_t*)d.dcv.p, (const uint32_t*)d.acbits.p, nb, nbi, blob, (u64*)d.bits.p);
     if (!d.scan((const u64*)d.bits.p, (u64*)d.off.p, (size_t)nb + 1, s)) return false;

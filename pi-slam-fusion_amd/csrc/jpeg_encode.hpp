@@ -284,11 +284,15 @@ public:
     JpegEncoder(const JpegEncoder&) = delete;
     JpegEncoder& operator=(const JpegEncoder&) = delete;
     bool encode(const void* dev_bgr, int n, const int* slots, size_t image_stride, int rows, int cols, size_t step, int quality, size_t* offsets, void* stream);
+    // the same for n windows of rows x cols pixels anywhere in one allocation: window i begins byte_offsets[i] bytes behind dev_base
+    // (64 bits: a tile of a mosaic of any size; the tiles of a pyramid TIFF, overview.hip)
+    bool encode_windows(const void* dev_base, int n, const long long* byte_offsets, int rows, int cols, size_t step, int quality, size_t* offsets, void* stream);
     bool fetch(uint8_t* out, void* stream);
     // the same into a page-locked buffer of the encoder's own (grow-only, valid until the next call; nullptr on failure): for a
     // caller that only passes the bytes on -- save() writes them to the file -- and would otherwise land them in pageable memory
     const uint8_t* fetch_pinned(void* stream);
 private:
+    bool encode_at(const void* dev_bgr, int n, const int* slots, const long long* where, size_t image_stride, int rows, int cols, size_t step, int quality, size_t* offsets, void* stream);
     struct Impl;
     Impl* p_ = nullptr;
 };

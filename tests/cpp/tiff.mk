@@ -1,0 +1,13 @@
+# AddressSanitizer + UndefinedBehaviorSanitizer build of the host TIFF writer (csrc/tiff_pyramid.hpp through image_io.cpp's entry
+# points; no HIP, plain g++):   make -C tests/cpp -f tiff.mk   -> build/san_tiff, driven by tests/test_tiff.py
+CXX   ?= g++
+ROOT  := ../..
+SRC   := $(ROOT)/pi-slam-fusion_amd/csrc
+HOST  := $(SRC)/jpeg_decode.cpp $(SRC)/png_decode.cpp $(SRC)/image_io.cpp
+HDRS  := $(SRC)/jpeg_decode.hpp $(SRC)/jpeg_encode.hpp $(SRC)/tiff_pyramid.hpp $(ROOT)/include/pifusion.h
+FLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall -I$(SRC) -I$(ROOT)/include
+OUT   ?= build
+
+$(OUT)/san_tiff: san_tiff.cpp $(HOST) $(HDRS)
+	mkdir -p $(OUT)
+	$(CXX) $(FLAGS) -fsanitize=address,undefined -fno-sanitize-recover=all san_tiff.cpp $(HOST) -o $@ -lz -lpthread

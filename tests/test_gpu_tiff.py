@@ -1,0 +1,205 @@
+"""The pyramid TIFF made on the GPU (csrc/overview.hip: overview chain and empty test; jpeg_encode.hip: the tiles) against the host writer
+(csrc/tiff_pyramid.hpp, itself pinned to the format by tests/test_tiff.py): byte-equal files.  First for images of any size in device
+memory (pf_tiff_write_device: odd sizes and the repeat rule at every depth), then for its users: save("m.tif") of a map, of a map with
+holes, of a single-band map, of a sharded map, and an image wider than a JPEG can be."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import jpeg_encode_model as model
+import tiff_model as tm
+from helpers import jitter_poses, workloads
+from test_gpu_jpeg_encode import build_map
+from test_tiff import XF, encoder, with_background
+
+pytestmark = pytest.mark.gpu
+
+
+def device_file(pf, path, a, q=95, bg=0, xf=None, big=False, step=0, stream=None):
+    import torch
+    h, w = a.shape[:2]
+    if step:
+        buf = torch.full((h, step), 0x5A, dtype=torch.uint8, device="cuda")
+        buf[:, :3 * w] = torch.from_numpy(np.ascontiguousarray(a).reshape(h, 3 * w)).cuda()
+    else:
+        buf = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    torch.cuda.synchronize()
+    assert pf.tiff_write_device(path, buf.data_ptr(), h, w, q, bg, xf, big, step, stream), pf.lib().pf_last_error()
+    return open(path, "rb").read()
+
+
+def host_file(pf, path, a, q=95, bg=0, xf=None, big=False):
+    assert pf.tiff_write(path, a, q, bg, xf, big)
+    return open(path, "rb").read()
+
+
+def transform_of(g, org):
+    """pixel (column, row) -> plane metres, from pf_grid and save_to_memory's origin tile (stable tile coordinates: dense index + off)"""
+    dims, geo = g.grid()
+    lp, ele = geo[5], geo[4]
+    return [lp, 0, 0, geo[0] + (org[0] - dims[2]) * ele, 0, lp, 0, geo[1] + (org[1] - dims[3]) * ele, 0, 0, 1, 0, 0, 0, 0, 1]
+
+
+def test_device_file_equals_host_file_sweep(pf, tmp_path):
+    import torch
+    rng = np.random.default_rng(20261016)
+    shapes = [(1, 1), (255, 257), (256, 256), (300, 1000), (3000, 4000), (512, 1024), (257, 513)] + [tuple(int(v) for v in rng.integers(1, 700, 2)) for _ in range(24)]
+    kinds = ("noise", "smooth", "steps", "zero", "white")
+    side = torch.cuda.Stream()
+    d, h_ = str(tmp_path / "d.tif"), str(tmp_path / "h.tif")
+    for n, (h, w) in enumerate(shapes):
+        q = (95, 30)[n % 2]; bg = (0, 255)[(n // 2) % 2]
+        a = model.content(h, w, kinds[n % len(kinds)] if h * w < 10 ** 6 else "noise", n)
+        if n % 3 != 1:
+            a = with_background(a, bg)
+        xf = XF if n % 2 else None
+        want = host_file(pf, h_, a, q, bg, xf, n % 7 == 3)
+        got = device_file(pf, d, a, q, bg, xf, n % 7 == 3)
+        assert got == want, ("packed", h, w, q, bg)
+        if n % 4 == 0:
+            assert device_file(pf, d, a, q, bg, xf, n % 7 == 3, step=3 * w + 1 + n % 29) == want, ("padded step", h, w)
+        if n % 4 == 1:
+            assert device_file(pf, d, a, q, bg, xf, n % 7 == 3, step=3 * w + 16 - (3 * w) % 16) == want, ("aligned padded step", h, w)
+        if n % 5 == 0:
+            assert device_file(pf, d, a, q, bg, xf, n % 7 == 3, stream=side.cuda_stream) == want, ("side stream", h, w)
+    # and the file is what the format says, not only what the host writer says
+    a = with_background(model.content(1100, 2100, "noise", 5), 255)
+    tm.check_file(device_file(pf, d, a, 95, 255, XF), a, 255, encoder(pf, 95), XF)
+
+
+def test_device_file_wider_than_a_jpeg_can_be(pf, tmp_path):
+    """256 x 65 792: image 8 is 1 x 257 and image 9 is 1 x 129, the odd case at depth.  (Stands in for a map that wide: at 256 pixels per
+    tile such a map needs more than 257 tiles in a row, i.e. keyframes along a line of that length, which does not fit a test's minute.)"""
+    h, w = 256, 65792
+    y, x = np.mgrid[0:h, 0:w]
+    a = np.stack([(x // 7 + y) % 256, (x // 300 * 37 + y * 2) % 256, (x + y * 3) % 251], -1).astype(np.uint8)
+    a[:, 20000:30000] = 0
+    want = host_file(pf, str(tmp_path / "h.tif"), a)
+    assert device_file(pf, str(tmp_path / "d.tif"), a) == want
+    assert len(tm.parse(want)[1]) == 10
+
+
+def test_device_writer_refuses_what_it_cannot_do(pf, tmp_path):
+    import torch
+    L = pf.lib()
+    a = model.content(40, 56, "noise", 1)
+    dev = torch.from_numpy(a).cuda()
+    f = str(tmp_path / "x.tif").encode()
+    assert L.pf_tiff_write_device(f, None, 40, 56, 0, 95, 0, None, 0, None) == 0
+    assert L.pf_tiff_write_device(f, dev.data_ptr(), 0, 56, 0, 95, 0, None, 0, None) == 0
+    assert L.pf_tiff_write_device(f, dev.data_ptr(), 40, 56, 100, 95, 0, None, 0, None) == 0 and b"step" in L.pf_last_error()
+    assert L.pf_tiff_write_device(f, a.ctypes.data, 40, 56, 0, 95, 0, None, 0, None) == 0 and b"device memory" in L.pf_last_error()
+    assert not os.path.exists(f.decode())
+    g = str(tmp_path / "missing" / "x.tif").encode()
+    assert L.pf_tiff_write_device(g, dev.data_ptr(), 40, 56, 0, 95, 0, None, 0, None) == 0 and b"cannot open" in L.pf_last_error()
+    assert L.pf_tiff_write_device(f, dev.data_ptr(), 40, 56, 0, 95, 0, None, 0, None) == 1
+
+
+@pytest.mark.parametrize("ff,bands,bg", [(0, 5, 0), (1, 5, 255), (0, 0, 255), (1, 0, 0)])
+def test_save_tif_is_the_host_file_of_the_mosaic(pf, orc, tmp_path, ff, bands, bg):
+    """save("m.tif") == pf_tiff_write_bgr(save_to_memory, 95, bg, transform, 0); the other extensions and the map itself are as they were"""
+    from PIL import Image
+    g, o = build_map(pf, orc, ff, bands, bg)
+    ref, oorg = o.save()
+    mem, org = g.save_to_memory()
+    assert org == oorg and np.array_equal(mem, ref)
+    xf = transform_of(g, org)
+    g.blend_changed()                                                     # clears Ischanged: what follows must not be touched by the save
+    tiles = g.tiles()
+    before = g.blend_tiles(tiles)
+    h_ = str(tmp_path / "host.tif")
+    want = host_file(pf, h_, mem, 95, bg, xf)
+    for name in ("m.tif", "m.TIFF"):
+        f = str(tmp_path / name)
+        assert g.save(f)
+        assert open(f, "rb").read() == want, name
+    tm.check_file(want, mem, bg, encoder(pf, 95), xf, big=False)
+    f = str(tmp_path / "q30.tif")
+    assert g.save_tiff(f, 30) and open(f, "rb").read() == host_file(pf, h_, mem, 30, bg, xf)
+    assert g.save_tiff(f, 95, True) and open(f, "rb").read() == host_file(pf, h_, mem, 95, bg, xf, True)
+    assert g.save(str(tmp_path / "m.tif")) and open(str(tmp_path / "m.tif"), "rb").read() == want          # the options do not stick
+    # the map, its flags and the other formats are as before
+    assert g.blend_changed()[0] == [] and np.array_equal(g.blend_tiles(tiles), before)
+    again, org2 = g.save_to_memory()
+    assert org2 == org and np.array_equal(again, ref)
+    for name in ("m.jpg", "m.JPEG"):
+        f = str(tmp_path / name)
+        assert g.save(f)
+        assert open(f, "rb").read() == pf.jpeg_encode(mem, 95), name
+    for ext in (".png", ".ppm"):
+        f = str(tmp_path / ("m" + ext))
+        assert g.save(f)
+        assert np.array_equal(np.asarray(Image.open(f).convert("RGB"))[:, :, ::-1], ref)
+    assert not g.save(str(tmp_path / "missing" / "x.tif")) and not g.save(str(tmp_path / "missing" / "x.jpg"))
+    g.close()
+
+
+@pytest.mark.parametrize("bg", [0, 255])
+def test_map_with_holes_shares_the_empty_stream_across_levels(pf, tmp_path, bg):
+    """two sorties far apart on a diagonal: the mosaic's bounding box has tile slots without a map tile"""
+    wl = workloads()
+    cam = [640, 480, 500, 500, 320, 240]
+    a = jitter_poses(3, seed=5)
+    b = [[p[0] + 300.0, p[1] + 250.0] + list(p[2:]) for p in jitter_poses(3, seed=6)]
+    g = pf.Map2D.create(pf.TypeMultiBandCPU, False, bg_color=bg)
+    assert g.prepare(wl.IDENTITY_PLANE, cam, a)
+    for k, p in enumerate(a + b):
+        assert g.feed(wl.smooth_frame(480, 640, k) ^ (wl.noise_frame(480, 640, 300 + k) >> 3), p)
+    mem, org = g.save_to_memory()
+    slots = (mem.shape[0] // 256) * (mem.shape[1] // 256)
+    assert slots > len(g.tiles())                                         # holes
+    xf = transform_of(g, org)
+    f = str(tmp_path / "holes.tif")
+    assert g.save(f)
+    data = open(f, "rb").read()
+    assert data == host_file(pf, str(tmp_path / "h.tif"), mem, 95, bg, xf)
+    ni, nt, ne = tm.check_file(data, mem, bg, encoder(pf, 95), xf)
+    _, ifds = tm.parse(data)
+    empties = [[tm.is_empty(t, bg) for t in tm.tiles_of(lv)] for lv in tm.chain(mem)]
+    assert sum(any(e) for e in empties) >= 2 and ne >= slots - len(g.tiles())
+    shared = {s for lv, ifd in zip(empties, ifds) for e, s in zip(lv, tm.tile_streams(data, ifd)) if e}
+    assert len(shared) == 1
+    g.close()
+
+
+def test_single_band_map_saves_tif_through_the_host_writer(pf, tmp_path):
+    wl = workloads()
+    cam = [640, 480, 500, 500, 320, 240]
+    poses = jitter_poses(4, seed=3)
+    g = pf.Map2D.create(pf.TypeCPU, False)
+    assert g.prepare(wl.IDENTITY_PLANE, cam, poses)
+    for k, p in enumerate(poses):
+        assert g.feed(wl.smooth_frame(480, 640, k), p)
+    mem, org = g.save_to_memory()
+    f = str(tmp_path / "s.tif")
+    assert g.save(f) and open(f, "rb").read() == host_file(pf, str(tmp_path / "h.tif"), mem, 95, 0, transform_of(g, org))
+    g.close()
+
+
+def test_dist_save_tif_on_rank_0_equals_the_unsharded_file(pf, orc, tmp_path):
+    from test_gpu_dist import Rendezvous, collective, workload
+    sh = importlib.import_module("pi_slam_fusion_amd.sharding")
+    wl = workloads()
+    cam, poses, frames = workload(wl)
+    world = 2
+    whole = pf.Map2D.create(pf.TypeMultiBandCPU, False, scale=2.0)
+    maps = [pf.Map2D.create(pf.TypeMultiBandCPU, False, scale=2.0, shard_rank=r, shard_count=world, shard_block=1) for r in range(world)]
+    for m in maps + [whole]:
+        assert m.prepare(wl.IDENTITY_PLANE, cam, poses[:2])
+        for f, p in zip(frames, poses):
+            assert m.feed(f, p)
+    rv = Rendezvous(world)
+    dms = [sh.DistMap(m, r, world, backend="host", exchange=rv.fn(r)) for r, m in enumerate(maps)]
+    names = [str(tmp_path / ("rank%d.tif" % r)) for r in range(world)]
+    assert collective(world, rv, lambda r: dms[r].save(names[r])) == [True] * world
+    one = str(tmp_path / "whole.tif")
+    assert whole.save(one)
+    mem, org = whole.save_to_memory()
+    assert open(names[0], "rb").read() == open(one, "rb").read() == host_file(pf, str(tmp_path / "h.tif"), mem, 95, 0, transform_of(whole, org))
+    assert not os.path.exists(names[1])                                   # the other ranks hold no picture
+    for d in dms:
+        d.close()
+    for m in maps + [whole]:
+        m.close()

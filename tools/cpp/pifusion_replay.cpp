@@ -3,7 +3,7 @@
 //     pifusion_replay <datapath> [key=value ...]
 //
 // keys are the reference's svar names: Map2D.Type (3), Map2D.Thread (1), PrepareFrameNum (10), Video.fps (100, 0 = unpaced),
-// Map.File2Save, MultiBandMap2DCPU.ForceFloat, MultiBandMap2DCPU.BandNumber, Map2D.Scale, Result.BackGroundColor ...
+// Map.File2Save (x.png / x.jpg / x.tif -- the tiled pyramid TIFF with overviews and geo tags, pf_save -- else PPM), MultiBandMap2DCPU.ForceFloat, MultiBandMap2DCPU.BandNumber, Map2D.Scale, Result.BackGroundColor ...
 // Build: g++ -std=c++11 -Iinclude tools/cpp/pifusion_replay.cpp -Lpi-slam-fusion_amd -l:libpifusion.so -lpthread
 #include <pifusion/TestSystem.h>
 
