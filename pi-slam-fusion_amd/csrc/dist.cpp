@@ -373,57 +373,73 @@ int DistMap::blend_changed(int* xy, uint8_t* bgr, int cap)
     return (int)mine.size();
 }
 
-// save() across ranks: tiles travel once to rank 0, which collapses the whole mosaic (.cpp:779-847).  On the other ranks the
-// call returns true with rows = cols = 0 (they hold no picture).
-bool DistMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const char* jpeg)
+static double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+
+// save() across ranks: tiles travel once to rank 0, which collapses the whole mosaic (.cpp:779-847).  The collective part comes in two
+// steps.  First every rank's tile list on every rank: the extent of the whole mosaic is known from the lists alone.
+bool DistMap::save_lists(SaveGather& g)
 {
-    const auto t_begin = std::chrono::steady_clock::now();
-    if (!m_->use_device()) return false;
-    const int n = t_->nranks, me = t_->rank;
-    if (n == 1) return m_->save_to_memory(bgr, rows, cols, tx0, ty0, nullptr, jpeg);
-    std::vector<std::vector<FusionMap::TileRec>> all;
+    g.t_begin = std::chrono::steady_clock::now();
     std::vector<long long> caps;
-    if (!gather_lists(all, caps, 0)) return false;
+    if (!gather_lists(g.all, caps, 0)) return false;
+    int mnx = 1 << 30, mny = 1 << 30, mxx = -(1 << 30), mxy = -(1 << 30);
+    for (auto& l : g.all) for (auto& t : l) { g.count++; mnx = std::min(mnx, t.ix); mny = std::min(mny, t.iy); mxx = std::max(mxx, t.ix); mxy = std::max(mxy, t.iy); }
+    if (g.count) { g.rows = (mxy + 1 - mny) * kElePixels; g.cols = (mxx + 1 - mnx) * kElePixels; g.tx0 = mnx; g.ty0 = mny; }
+    return true;
+}
+
+// ... then the tiles themselves: g.foreign is where they lie on rank 0 (the other ranks hold no picture and are done after this)
+bool DistMap::save_tiles(SaveGather& g)
+{
+    const int n = t_->nranks, me = t_->rank;
     const size_t nb = m_->tile_bytes();
-    // query (bgr == nullptr): the extent is known from the lists alone
-    if (!bgr && !jpeg) {
-        int mnx = 1 << 30, mny = 1 << 30, mxx = -(1 << 30), mxy = -(1 << 30), cnt = 0;
-        for (auto& l : all) for (auto& t : l) { cnt++; mnx = std::min(mnx, t.ix); mny = std::min(mny, t.iy); mxx = std::max(mxx, t.ix); mxy = std::max(mxy, t.iy); }
-        if (!cnt) return false;
-        if (me == 0) { *rows = (mxy + 1 - mny) * kElePixels; *cols = (mxx + 1 - mnx) * kElePixels; *tx0 = mnx; *ty0 = mny; }
-        else { *rows = *cols = 0; *tx0 = *ty0 = 0; }
-        return true;
-    }
     std::vector<const void*> s(n, nullptr); std::vector<void*> r(n, nullptr);
     std::vector<size_t> sb(n, 0), rb(n, 0);
     stats_ = {};
     if (me != 0) {
         std::vector<std::pair<int, int>> mine;
-        for (auto& t : all[me]) mine.push_back({ t.ix, t.iy });
+        for (auto& t : g.all[me]) mine.push_back({ t.ix, t.iy });
         const bool ok_here = send_.reserve(nb * mine.size() + 256) && m_->export_tiles(mine, send_.p);
         if (!agree(ok_here)) return false;
         s[0] = send_.p; sb[0] = nb * mine.size();
         if (!exchange_checked(s, sb, r, rb, "save tiles")) return false;
         stats_.bytes_sent = sb[0]; stats_.tiles = mine.size();
-        *rows = *cols = 0; *tx0 = *ty0 = 0;
-        stats_.exchange_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        return true;
+    } else {
+        size_t total = 0;
+        std::vector<size_t> off(n, 0);
+        for (int p = 1; p < n; p++) { off[p] = total; total += nb * g.all[p].size(); }
+        if (!agree(recv_.reserve(total + 256))) return false;
+        for (int p = 1; p < n; p++) { r[p] = (char*)recv_.p + off[p]; rb[p] = nb * g.all[p].size(); }
+        if (!exchange_checked(s, sb, r, rb, "save tiles")) return false;
+        for (int p = 1; p < n; p++)
+            for (size_t k = 0; k < g.all[p].size(); k++) g.foreign.push_back({ g.all[p][k].ix, g.all[p][k].iy, (char*)recv_.p + off[p] + k * nb });
+        stats_.bytes_received = total; stats_.tiles = g.foreign.size();
     }
-    size_t total = 0;
-    std::vector<size_t> off(n, 0);
-    for (int p = 1; p < n; p++) { off[p] = total; total += nb * all[p].size(); }
-    if (!agree(recv_.reserve(total + 256))) return false;
-    for (int p = 1; p < n; p++) { r[p] = (char*)recv_.p + off[p]; rb[p] = nb * all[p].size(); }
-    if (!exchange_checked(s, sb, r, rb, "save tiles")) return false;
-    const auto t_x = std::chrono::steady_clock::now();
-    std::vector<FusionMap::ForeignTile> foreign;
-    for (int p = 1; p < n; p++)
-        for (size_t k = 0; k < all[p].size(); k++) foreign.push_back({ all[p][k].ix, all[p][k].iy, (char*)recv_.p + off[p] + k * nb });
-    const bool ok = m_->save_to_memory(bgr, rows, cols, tx0, ty0, &foreign, jpeg);
-    stats_.bytes_received = total; stats_.tiles = foreign.size();
-    stats_.exchange_ms = std::chrono::duration<double, std::milli>(t_x - t_begin).count();
-    stats_.compute_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_x).count();
-    return ok;
+    stats_.exchange_ms = ms_since(g.t_begin);
+    return true;
+}
+
+// pf_dist_save_to_memory, two calls as pf_save_to_memory: bgr == nullptr reports the extent.  On the ranks other than 0 both
+// return true with rows = cols = 0.
+bool DistMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
+{
+    if (!m_->use_device()) return false;
+    if (t_->nranks == 1) return m_->save_to_memory(bgr, rows, cols, tx0, ty0);
+    SaveGather g;
+    if (!save_lists(g)) return false;
+    if (bgr ? !save_tiles(g) : !g.count) return false;
+    if (t_->rank != 0) { *rows = *cols = 0; *tx0 = *ty0 = 0; return true; }
+    FusionMap::SaveTarget t;
+    if (bgr) {
+        t.kind = FusionMap::SaveTarget::Buffer; t.bgr = bgr;
+        const auto t_x = std::chrono::steady_clock::now();
+        const bool ok = m_->save_mosaic(t, &g.foreign);
+        stats_.compute_ms = ms_since(t_x);
+        if (!ok) return false;
+        g.rows = t.rows; g.cols = t.cols; g.tx0 = t.tx0; g.ty0 = t.ty0;
+    }
+    *rows = g.rows; *cols = g.cols; *tx0 = g.tx0; *ty0 = g.ty0;
+    return true;
 }
 
 // Map2D::feed across ranks (SURVEY 8e "one H2D + P2P over xGMI"): the tracker hands its keyframe to ONE rank (`root`,
@@ -471,32 +487,18 @@ int DistMap::feed(const pf_image* img, const double pose7[7], int root, const Fu
     return rendered ? 1 : 0;
 }
 
+// every rank makes the call (the gather is collective); rank 0 writes the file, by the same route a map of its own would take
 bool DistMap::save(const char* filename)
 {
-    int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
-    if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
-    if (is_tiff_name(filename) && m_->single_band()) {          // gathered as pixels, written by the host writer with the map's geo tags
-        std::vector<uint8_t> img((size_t)rows * cols * 3 + 1);
-        if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
-        if (t_->rank != 0) return true;
-        double xf[16];
-        m_->tiff_transform(tx0, ty0, xf);
-        if (!write_tiff_file("save", filename, img.data(), rows, cols, 0, 95, m_->bg_color(), xf, false)) return false;
-        std::printf("Resolution:[%d %d]\n", cols, rows);
-        return true;
-    }
-    if ((is_jpeg_name(filename) || is_tiff_name(filename)) && !m_->single_band()) {          // rank 0 encodes the gathered mosaic on its GPU (every rank takes this branch: the exchange is collective)
-        if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0, filename)) return false;          // rank 0's map writes the file
-        if (t_->rank != 0) return true;
-        std::printf("Resolution:[%d %d]\n", cols, rows);
-        return true;
-    }
-    std::vector<uint8_t> img((size_t)rows * cols * 3 + 1);
-    if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
+    if (!m_->use_device()) return false;
+    if (t_->nranks == 1) return m_->save(filename);
+    SaveGather g;
+    if (!save_lists(g) || !g.count || !save_tiles(g)) return false;
     if (t_->rank != 0) return true;
-    if (!write_image_file(filename, img.data(), rows, cols)) return false;
-    std::printf("Resolution:[%d %d]\n", cols, rows);
-    return true;
+    const auto t_x = std::chrono::steady_clock::now();
+    const bool ok = m_->save_file(filename, save_route(filename, m_->single_band()), 95, false, &g.foreign);
+    stats_.compute_ms = ms_since(t_x);
+    return ok;
 }
 
 }  // namespace pf

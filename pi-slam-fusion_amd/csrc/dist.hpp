@@ -2,6 +2,7 @@
 #pragma once
 #include "fusion_map.hpp"
 #include "dist_plan.hpp"
+#include <chrono>
 
 namespace pf {
 
@@ -27,7 +28,7 @@ public:
     DistMap(FusionMap* m, Transport* t);      // takes the transport
     ~DistMap();
     int  blend_changed(int* xy, uint8_t* bgr, int cap);        // tiles blended on this rank, -1 on failure
-    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const char* jpeg_file = nullptr);      // jpeg_file: see FusionMap::save_to_memory
+    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0);
     bool save(const char* filename);
     // 1 rendered / accepted, 0 rejected, -1 failure.  `produce` (root only, img->data == nullptr): the root's pixels are written into its
     // staged slot by the caller's own work on the map's stream (pf_dist_feed_jpeg: the decoder) instead of being uploaded
@@ -38,6 +39,15 @@ public:
     void set_verify(bool on) { verify_ = on; }
 private:
     bool gather_lists(std::vector<std::vector<FusionMap::TileRec>>& all, std::vector<long long>& caps, long long my_cap);
+    // a save's gather: every rank's list and the extent they span, then (rank 0) the other ranks' tiles in recv_
+    struct SaveGather {
+        std::chrono::steady_clock::time_point t_begin;
+        std::vector<std::vector<FusionMap::TileRec>> all;
+        size_t count = 0; int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
+        std::vector<FusionMap::ForeignTile> foreign;
+    };
+    bool save_lists(SaveGather& g);
+    bool save_tiles(SaveGather& g);
     bool agree(bool ok_here);
     bool exchange_checked(const std::vector<const void*>& send, const std::vector<size_t>& sb, const std::vector<void*>& recv,
                           const std::vector<size_t>& rb, const char* what);

@@ -2195,13 +2195,19 @@ bool FusionMap::blend_batch_per_level(const std::vector<std::pair<int, int>>& ti
 
 #endif
 
+// a single-band tile's pixels (BGRA, Map2DCPU) as the three bytes the outputs carry
+static void bgra_to_bgr(const uint8_t* bgra, uint8_t* bgr, size_t n)
+{
+    for (size_t i = 0; i < n; i++) { bgr[3 * i] = bgra[4 * i]; bgr[3 * i + 1] = bgra[4 * i + 1]; bgr[3 * i + 2] = bgra[4 * i + 2]; }
+}
+
 bool FusionMap::blend_tile(int ix, int iy, void* raw, uint8_t* bgr, const void* const* halo)
 {
     if (single_band_) {          // the Map2DCPU tile is displayable as is (glTexImage2D GL_BGRA, Map2DCPU.cpp:497-503)
         std::vector<uint8_t> px((size_t)kElePixels * kElePixels * 4);
         if (!get_tile_bgra(ix, iy, px.data())) return false;
         if (raw) std::memcpy(raw, px.data(), px.size());
-        if (bgr) for (size_t i = 0; i < (size_t)kElePixels * kElePixels; i++) { bgr[3 * i] = px[4 * i]; bgr[3 * i + 1] = px[4 * i + 1]; bgr[3 * i + 2] = px[4 * i + 2]; }
+        if (bgr) bgra_to_bgr(px.data(), bgr, (size_t)kElePixels * kElePixels);
         return true;
     }
     std::lock_guard<std::mutex> l(mu_); (void)drain();
@@ -2263,8 +2269,7 @@ int FusionMap::blend_changed(int* xy, uint8_t* bgr, int cap)
         for (size_t i = 0; i < tiles.size(); i++) {
             Tile* t = store_.find(tiles[i].first, tiles[i].second);
             if (hipMemcpy(px.data(), t->base, px.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-            uint8_t* d = bgr + i * tile_px;
-            for (size_t k = 0; k < (size_t)kElePixels * kElePixels; k++) { d[3 * k] = px[4 * k]; d[3 * k + 1] = px[4 * k + 1]; d[3 * k + 2] = px[4 * k + 2]; }
+            bgra_to_bgr(px.data(), bgr + i * tile_px, (size_t)kElePixels * kElePixels);
             xy[2 * i] = tiles[i].first; xy[2 * i + 1] = tiles[i].second;
             t->changed = false;
         }
@@ -2280,72 +2285,72 @@ int FusionMap::blend_changed(int* xy, uint8_t* bgr, int cap)
 
 // ------------------------------------------------------------------- save
 // MultiBandMap2DCPU::save (.cpp:779-847): paste all tiles per level, collapse
-// the whole mosaic once, 8U, background where level-0 weight is 0.
-bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const std::vector<ForeignTile>* foreign, const char* jpeg)
+// the whole mosaic once, 8U, background where level-0 weight is 0.  Everything between the extent and the hand-over of the
+// pixels happens under one hold of mu_: the buffer a target is given and the mosaic written into it have the same extent.
+bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* foreign)
 {
     std::lock_guard<std::mutex> l(mu_); (void)drain();
     if (!init_ok_ || !valid_ || !set_device()) return false;
     if (w_ == 0 || h_ == 0) return false;
     Section sec(this, T_SAVE);
     int mnx = 1000000, mny = 1000000, mxx = -1000000, mxy = -1000000, cnt = 0;
-    store_.for_each([&](int ix, int iy, Tile& t) {
-        if (t.fresh) return;
+    store_.for_each([&](int ix, int iy, Tile& tile) {
+        if (tile.fresh) return;
         cnt++; mnx = std::min(mnx, ix); mny = std::min(mny, iy); mxx = std::max(mxx, ix); mxy = std::max(mxy, iy);
     });
-    // tiles of other ranks gathered for this save (dist.cpp): they take part in the mosaic without entering the store
     if (foreign) for (auto& f : *foreign) { cnt++; mnx = std::min(mnx, f.ix); mny = std::min(mny, f.iy); mxx = std::max(mxx, f.ix); mxy = std::max(mxy, f.iy); }
     if (!cnt) return false;
     const int wx = mxx + 1 - mnx, wy = mxy + 1 - mny;
-    *rows = wy * kElePixels; *cols = wx * kElePixels; *tx0 = mnx; *ty0 = mny;
-    if (!bgr && !jpeg) return true;
-    if (jpeg && (bgr || single_band_)) { set_error("save: the stream of a mosaic in HBM was asked for where there is none"); return false; }
-    const bool tiff = jpeg && (tiff_forced_ || is_tiff_name(jpeg));
-    const int tiff_q = tiff_forced_ ? tiff_quality_ : 95;
-    const bool tiff_big = tiff_forced_ && tiff_big_;
-    tiff_forced_ = false;
-    if (jpeg && !tiff && !jpeg_size_ok("save", *rows, *cols)) return false;
+    t.rows = wy * kElePixels; t.cols = wx * kElePixels; t.tx0 = mnx; t.ty0 = mny;
+    for (double& v : t.transform) v = 0;
+    t.transform[0] = length_pixel_; t.transform[3] = min_[0] + (mnx - off_x_) * ele_size_;
+    t.transform[5] = length_pixel_; t.transform[7] = min_[1] + (mny - off_y_) * ele_size_;
+    t.transform[10] = 1; t.transform[15] = 1;
+    if (t.kind == SaveTarget::Extent) return true;
+    const bool file = t.kind == SaveTarget::File;
+    if (file && single_band_) { set_error("save: the stream of a mosaic in HBM was asked for where there is none"); return false; }
+    if (file && t.route == SaveRoute::DeviceJpeg && !jpeg_size_ok("save", t.rows, t.cols)) return false;          // before anything is made: no file
+    const size_t out_bytes = (size_t)t.rows * t.cols * 3;
+    if (t.kind == SaveTarget::Image) t.image->resize(out_bytes);
+    uint8_t* const bgr = file ? nullptr : t.kind == SaveTarget::Image ? t.image->data() : t.bgr;
     if (single_band_) {          // Map2DCPU::save (Map2DCPU.cpp:523-563): paste the tiles; holes are zero here
         HIP_OK(sync_all());
-        std::memset(bgr, 0, (size_t)*rows * *cols * 3);
+        std::memset(bgr, 0, out_bytes);
         std::vector<uint8_t> px((size_t)kElePixels * kElePixels * 4);
         bool ok = true;
-        store_.for_each([&](int ix, int iy, Tile& t) {
-            if (t.fresh || !ok) return;
-            if (hipMemcpy(px.data(), t.base, px.size(), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; return; }
-            for (int r = 0; r < kElePixels; r++) {
-                uint8_t* d = bgr + (((size_t)(iy - mny) * kElePixels + r) * *cols + (size_t)(ix - mnx) * kElePixels) * 3;
-                const uint8_t* sp = px.data() + (size_t)r * kElePixels * 4;
-                for (int c = 0; c < kElePixels; c++) { d[3 * c] = sp[4 * c]; d[3 * c + 1] = sp[4 * c + 1]; d[3 * c + 2] = sp[4 * c + 2]; }
-            }
+        store_.for_each([&](int ix, int iy, Tile& tile) {
+            if (tile.fresh || !ok) return;
+            if (hipMemcpy(px.data(), tile.base, px.size(), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; return; }
+            for (int r = 0; r < kElePixels; r++)
+                bgra_to_bgr(px.data() + (size_t)r * kElePixels * 4, bgr + (((size_t)(iy - mny) * kElePixels + r) * t.cols + (size_t)(ix - mnx) * kElePixels) * 3, kElePixels);
         });
         return ok;
     }
     const int L = band_num_;
     const size_t es = lay_.f32 ? 4 : 2, px = 3 * es;
     std::vector<uint64_t> tab((size_t)wx * wy, 0);
-    store_.for_each([&](int ix, int iy, Tile& t) { if (!t.fresh) tab[(size_t)(iy - mny) * wx + (ix - mnx)] = (uint64_t)(uintptr_t)t.base; });
+    store_.for_each([&](int ix, int iy, Tile& tile) { if (!tile.fresh) tab[(size_t)(iy - mny) * wx + (ix - mnx)] = (uint64_t)(uintptr_t)tile.base; });
     if (foreign) for (auto& f : *foreign) tab[(size_t)(f.iy - mny) * wx + (f.ix - mnx)] = (uint64_t)(uintptr_t)f.dev;
     HIP_OK(sync_all());
     if (!mosaic_table_.reserve(tab.size() * 8)) return false;
     HIP_OK(hipMemcpy(mosaic_table_.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    const size_t out_bytes = (size_t)*rows * *cols * 3;
     if (!blend_out_bgr_.reserve(out_bytes)) return false;
 #if PF_EXPERIMENTS
     static const bool per_level = exp_env("PF_BLEND_PER_LEVEL") != nullptr;
     if (per_level) {                              // rounds 1-5: paste per level, one collapse launch per level, finish
         for (int i = 0; i <= L; i++) {
-            const size_t n = (size_t)(*rows >> i) * (*cols >> i);
+            const size_t n = (size_t)(t.rows >> i) * (t.cols >> i);
             if (!blend_lv_[i].reserve(n * px)) return false;
             prof_begin(K_MOSAIC_GATHER, (double)n * px * 2);
             launch_mosaic_gather(stream_, lay_, i, (const uint64_t*)mosaic_table_.p, wx, wy, blend_lv_[i].p);
             prof_end();
         }
         for (int i = L; i > 0; i--) {
-            prof_begin(K_COLLAPSE, (double)(*rows >> (i - 1)) * (*cols >> (i - 1)) * px * 2.25);
-            launch_collapse(stream_, lay_.f32, blend_lv_[i - 1].p, 0, blend_lv_[i].p, 0, *rows >> (i - 1), *cols >> (i - 1), 1);
+            prof_begin(K_COLLAPSE, (double)(t.rows >> (i - 1)) * (t.cols >> (i - 1)) * px * 2.25);
+            launch_collapse(stream_, lay_.f32, blend_lv_[i - 1].p, 0, blend_lv_[i].p, 0, t.rows >> (i - 1), t.cols >> (i - 1), 1);
             prof_end();
         }
-        prof_begin(K_SAVE_FINISH, (double)*rows * *cols * (px + 4 + 3));
+        prof_begin(K_SAVE_FINISH, (double)t.rows * t.cols * (px + 4 + 3));
         launch_save_finish(stream_, lay_, blend_lv_[0].p, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
         prof_end();
         HIP_OK(sync_all());
@@ -2360,67 +2365,35 @@ bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int
     launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
     prof_end();
     HIP_OK(hipGetLastError());
-    if (tiff) {          // the mosaic stays where the collapse left it: overviews, empty test and tile streams are made from it there
-        double xf[16];
-        tiff_transform_locked(*tx0, *ty0, xf);
-        return tiff_dev_.write(jpeg, blend_out_bgr_.p, *rows, *cols, (size_t)*cols * 3, tiff_q, opt_.bg_color, xf, tiff_big, jpeg_enc_, stream_);
-    }
-    if (jpeg) {          // the mosaic stays where the collapse left it; cv::imwrite's JPEG defaults: quality 95, 4:2:0
-        size_t off[2];
-        if (!jpeg_enc_.encode(blend_out_bgr_.p, 1, nullptr, 0, *rows, *cols, (size_t)*cols * 3, 95, off, stream_)) return false;
-        const uint8_t* stream = jpeg_enc_.fetch_pinned(stream_);
-        return stream && write_bytes_file(jpeg, stream, off[1]);
-    }
-    if (!download({ { bgr, blend_out_bgr_.p, out_bytes } })) return false;
+    if (!file) return download({ { bgr, blend_out_bgr_.p, out_bytes } });
+    // the mosaic stays where the collapse left it
+    if (t.route == SaveRoute::DeviceTiff)          // overviews, empty test and tile streams are made from it there
+        return tiff_dev_.write(t.name, blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, t.quality, opt_.bg_color, t.transform, t.force_bigtiff, jpeg_enc_, stream_);
+    size_t off[2];                                 // cv::imwrite's JPEG defaults: quality 95, 4:2:0
+    if (!jpeg_enc_.encode(blend_out_bgr_.p, 1, nullptr, 0, t.rows, t.cols, (size_t)t.cols * 3, t.quality, off, stream_)) return false;
+    const uint8_t* stream = jpeg_enc_.fetch_pinned(stream_);
+    return stream && write_bytes_file(t.name, stream, off[1]);
+}
+
+bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
+{
+    SaveTarget t;
+    t.kind = bgr ? SaveTarget::Buffer : SaveTarget::Extent; t.bgr = bgr;
+    if (!save_mosaic(t)) return false;
+    *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
     return true;
 }
 
-void FusionMap::tiff_transform_locked(int tx0, int ty0, double out[16])
+bool FusionMap::save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign)
 {
-    for (int i = 0; i < 16; i++) out[i] = 0;
-    out[0] = length_pixel_; out[3] = min_[0] + (tx0 - off_x_) * ele_size_;
-    out[5] = length_pixel_; out[7] = min_[1] + (ty0 - off_y_) * ele_size_;
-    out[10] = 1; out[15] = 1;
-}
-void FusionMap::tiff_transform(int tx0, int ty0, double out[16])
-{
-    std::lock_guard<std::mutex> l(mu_);
-    tiff_transform_locked(tx0, ty0, out);
-}
-
-bool FusionMap::save_tiff(const char* filename, int quality, bool force_bigtiff)
-{
-    int rows, cols, tx0, ty0;
-    if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
-    if (!single_band_) {          // multi-band: made on the GPU from the mosaic in HBM
-        set_tiff_options(quality, force_bigtiff);
-        if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0, nullptr, filename)) { tiff_forced_ = false; return false; }
-    } else {
-        std::vector<uint8_t> img((size_t)rows * cols * 3);
-        if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
-        double xf[16];
-        tiff_transform(tx0, ty0, xf);
-        if (!write_tiff_file("save", filename, img.data(), rows, cols, 0, quality, opt_.bg_color, xf, force_bigtiff)) return false;
-    }
-    std::printf("Resolution:[%d %d]\n", cols, rows);
-    return true;
-}
-
-bool FusionMap::save(const char* filename)
-{
-    int rows, cols, tx0, ty0;
-    if (is_tiff_name(filename)) return save_tiff(filename, 95, false);
-    if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0)) return false;
-    if (is_jpeg_name(filename) && !single_band_) {          // multi-band: encoded on the GPU, only the stream is copied and written
-        if (!jpeg_size_ok("save", rows, cols)) return false;
-        if (!save_to_memory(nullptr, &rows, &cols, &tx0, &ty0, nullptr, filename)) return false;
-        std::printf("Resolution:[%d %d]\n", cols, rows);
-        return true;
-    }
-    std::vector<uint8_t> img((size_t)rows * cols * 3);
-    if (!save_to_memory(img.data(), &rows, &cols, &tx0, &ty0)) return false;
-    if (!write_image_file(filename, img.data(), rows, cols)) return false;
-    std::printf("Resolution:[%d %d]\n", cols, rows);
+    std::vector<uint8_t> img;
+    SaveTarget t;
+    if (route_on_device(route)) { t.kind = SaveTarget::File; t.name = filename; t.route = route; t.quality = quality; t.force_bigtiff = force_bigtiff; }
+    else { t.kind = SaveTarget::Image; t.image = &img; }
+    if (!save_mosaic(t, foreign)) return false;
+    if (route == SaveRoute::HostTiffGeo && !write_tiff_file("save", filename, img.data(), t.rows, t.cols, 0, quality, opt_.bg_color, t.transform, force_bigtiff)) return false;
+    if (route == SaveRoute::HostImage && !write_image_file(filename, img.data(), t.rows, t.cols)) return false;
+    std::printf("Resolution:[%d %d]\n", t.cols, t.rows);
     return true;
 }
 

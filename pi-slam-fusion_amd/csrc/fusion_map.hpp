@@ -6,6 +6,7 @@
 #include "kernels.hpp"
 #include "dist_plan.hpp"
 #include "env.hpp"
+#include "image_io.hpp"
 #include "jpeg_encode.hpp"
 #include "tiff_pyramid.hpp"
 #include <hip/hip_runtime.h>
@@ -106,19 +107,32 @@ public:
     unsigned queue_size();
     long read_back_last_frame(void* out, size_t cap);
     bool sync();
-    bool save(const char* filename);
-    // save("x.tif") with the tiles' JPEG quality and the flag that forces BigTIFF (pf_save_tiff); any file name
-    bool save_tiff(const char* filename, int quality, bool force_bigtiff);
-    // what the next save_to_memory(.., a .tif name) encodes with (DistMap::save sets them as save() does)
-    void set_tiff_options(int quality, bool force_bigtiff) { tiff_quality_ = quality; tiff_big_ = force_bigtiff; tiff_forced_ = true; }
-    // the 16 doubles of the file's ModelTransformationTag for a mosaic whose origin tile is (tx0, ty0)
-    void tiff_transform(int tx0, int ty0, double out[16]);
-    int  bg_color() const { return opt_.bg_color; }
+    // save(): the route comes from the name (save_route); save_tiff() (pf_save_tiff): a TIFF under any name, with the tiles' JPEG quality
+    // and the flag that forces BigTIFF.  Both are save_file() with the route chosen
+    bool save(const char* filename) { return save_file(filename, save_route(filename, single_band_), 95, false); }
+    bool save_tiff(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff); }
     struct ForeignTile { int ix, iy; const void* dev; };          // a tile slot image held outside the store (gathered for save)
-    // jpeg_file (bgr == nullptr): the collapsed mosaic stays in HBM and leaves as the JPEG stream save("x.jpg") writes
-    // (jpeg_encode.hip), which lands in the encoder's page-locked buffer and goes to that file; a name that ends in .tif / .tiff
-    // (or any name after set_tiff_options): the pyramid TIFF of overview.hip instead, from the same mosaic in HBM
-    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0, const std::vector<ForeignTile>* foreign = nullptr, const char* jpeg_file = nullptr);
+    // Where the collapsed mosaic of one save goes.  A value: what the caller asks for, and what save_mosaic() found out on the way
+    struct SaveTarget {
+        enum Kind { Extent,      // nowhere: rows, cols and the origin tile alone (the first call of pf_save_to_memory)
+                    Buffer,      // bgr: the caller's rows * cols * 3 bytes, sized from an earlier Extent call (its second call)
+                    Image,       // image: the library's own, sized inside the call from the extent the pixels are made for
+                    File };      // a file made on the GPU from the mosaic where it lies in HBM: name, route (a device route), quality, force_bigtiff
+        Kind kind = Extent;
+        uint8_t* bgr = nullptr;
+        std::vector<uint8_t>* image = nullptr;
+        const char* name = nullptr; SaveRoute route = SaveRoute::HostImage; int quality = 95; bool force_bigtiff = false;
+        // results
+        int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
+        double transform[16] = {};      // the ModelTransformationTag of a TIFF of this mosaic: pixel -> plane metres
+    };
+    // ONE pass under mu_: drains, takes the extent, collapses the mosaic and hands it to the target.  foreign: tiles of other ranks
+    // that take part without entering the store (dist.cpp)
+    bool save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* foreign = nullptr);
+    // save_mosaic() into the file: on the GPU, or as pixels through the route's host writer; prints the reference's "Resolution:" line
+    bool save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign = nullptr);
+    // the two-call protocol of pf_save_to_memory: bgr == nullptr reports the extent, bgr takes the pixels of the extent at that moment
+    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0);
 
     // seam exchange support (dist.cpp)
     using TileRec = pf::TileRec;        // dist_plan.hpp
@@ -368,9 +382,7 @@ private:
     DevBuf blend_lv_[kMaxLevels], blend_src_, blend_out_raw_, blend_out_bgr_, mosaic_table_, strip_desc_;
     // results on their way to the host: two pinned staging slots, filled on copy_stream_ while the host empties the other one
     static constexpr size_t kOutSlot = (size_t)32 << 20;
-    void tiff_transform_locked(int tx0, int ty0, double out[16]);
     TiffDevice  tiff_dev_;      // save("x.tif"): level buffers and flags of its own, tiles through jpeg_enc_
-    int  tiff_quality_ = 95; bool tiff_big_ = false, tiff_forced_ = false;
     JpegEncoder jpeg_enc_;      // save("x.jpg"), pf_blend_tiles_jpeg: reads blend_out_bgr_ on stream_, buffers of its own
     struct OutPiece { void* dst; const void* src; size_t bytes; };      // host destination, device source
     uint8_t*    out_pin_[2]{};
@@ -412,13 +424,5 @@ private:
 #endif
     double px_level0_ = 0, px_owned_ = 0;           // level-0 pixels computed (with halo) / tile pixels owned, over the frames rendered
 };
-
-// PNG (zlib) / PPM writer for save()
-bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int cols);
-bool is_jpeg_name(const char* filename);                                      // image_io.cpp
-bool is_tiff_name(const char* filename);
-bool write_tiff_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff);
-bool jpeg_size_ok(const char* who, int rows, int cols);
-bool write_bytes_file(const char* filename, const uint8_t* data, size_t len);
 
 }  // namespace pf

@@ -4,6 +4,7 @@
 // default, jpeg_encode.hpp) when it ends in .jpg / .jpeg, a tiled pyramid TIFF with JPEG tiles
 // (tiff_pyramid.hpp) when it ends in .tif / .tiff, binary PPM otherwise.
 #include "../../include/pifusion.h"
+#include "image_io.hpp"
 #include "jpeg_decode.hpp"
 #include "jpeg_encode.hpp"
 #include "tiff_pyramid.hpp"
@@ -20,8 +21,6 @@
 #include <zlib.h>
 
 namespace pf {
-
-bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int cols);      // also declared in fusion_map.hpp (save())
 
 static void put_be32(uint8_t* p, uint32_t v) { p[0] = v >> 24; p[1] = v >> 16; p[2] = v >> 8; p[3] = v; }
 
@@ -132,9 +131,15 @@ static bool name_ends(const char* filename, const char* ext)
     return true;
 }
 // the name ends in .jpg / .jpeg, in either case: cv::imwrite hands the image to its JPEG encoder
-bool is_jpeg_name(const char* filename) { return name_ends(filename, ".jpg") || name_ends(filename, ".jpeg"); }
+static bool is_jpeg_name(const char* filename) { return name_ends(filename, ".jpg") || name_ends(filename, ".jpeg"); }
 // ... in .tif / .tiff, in either case: the tiled pyramid TIFF (no reference counterpart: the reference writes none)
-bool is_tiff_name(const char* filename) { return name_ends(filename, ".tif") || name_ends(filename, ".tiff"); }
+static bool is_tiff_name(const char* filename) { return name_ends(filename, ".tif") || name_ends(filename, ".tiff"); }
+
+SaveRoute save_route(const char* filename, bool single_band)
+{
+    if (is_tiff_name(filename)) return tiff_route(single_band);
+    return is_jpeg_name(filename) && !single_band ? SaveRoute::DeviceJpeg : SaveRoute::HostImage;
+}
 
 bool write_tiff_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff)
 {

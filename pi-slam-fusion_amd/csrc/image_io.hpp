@@ -1,0 +1,27 @@
+// image_io.hpp -- what image_io.cpp (host only) offers the engine: the route of a save and the host writers
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace pf {
+
+// Who turns the collapsed mosaic into the file save() was asked for: the GPU encoders, which read it where it lies in HBM
+// (multi-band maps), or a host writer, which takes it as pixels.
+enum class SaveRoute {
+    DeviceJpeg,      // jpeg_encode.hip: only the stream comes to the host
+    DeviceTiff,      // overview.hip + jpeg_encode.hip: the tiled pyramid TIFF
+    HostTiffGeo,     // write_tiff_file with the map's quality, background and ModelTransformationTag (single-band maps)
+    HostImage,       // write_image_file: PNG, PPM, and a single-band map's JPEG
+};
+// THE decision, from the name's extension (either case) and the map's kind; pf_save_tiff's "a TIFF under any name" is tiff_route
+SaveRoute save_route(const char* filename, bool single_band);
+inline SaveRoute tiff_route(bool single_band) { return single_band ? SaveRoute::HostTiffGeo : SaveRoute::DeviceTiff; }
+inline bool route_on_device(SaveRoute r) { return r == SaveRoute::DeviceJpeg || r == SaveRoute::DeviceTiff; }
+
+// PNG (zlib) / PPM / JPEG / plain TIFF by the name, as cv::imwrite picks
+bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int cols);
+bool write_tiff_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff);
+bool jpeg_size_ok(const char* who, int rows, int cols);
+bool write_bytes_file(const char* filename, const uint8_t* data, size_t len);
+
+}  // namespace pf

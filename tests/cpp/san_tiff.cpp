@@ -3,8 +3,10 @@
 // bytes, so one byte read past it is a finding.
 //   san_tiff <dir>     every size 1...40 x 1...40 and a few around the tile edge: packed and padded rows give the same file,
 //                      classic and BigTIFF headers are what they say, the first tile's stream decodes at 256 x 256, a file
-//                      that cannot be opened leaves none.
+//                      that cannot be opened leaves none.  And the route of a save (save_route, image_io.cpp) for every kind of name,
+//                      single-band and multi-band.
 #include "pifusion.h"
+#include "image_io.hpp"
 #include "jpeg_decode.hpp"
 #include <cstdio>
 #include <cstdlib>
@@ -87,6 +89,17 @@ int main(int argc, char** argv)
     const std::string gone = dir + "/no/such/dir/x.tif";
     uint8_t px[3] = { 1, 2, 3 };
     if (pf_tiff_write_bgr(gone.c_str(), px, 1, 1, 0, 95, 0, nullptr, 0) || pf_tiff_write_bgr((dir + "/z.tif").c_str(), px, 1, 1, 2, 95, 0, nullptr, 0)) { std::printf("MISMATCH a bad call succeeded\n"); fails++; }
+    // who writes save(name): the extension decides, in either case; the GPU encoders serve multi-band maps only
+    using R = pf::SaveRoute;
+    const struct { const char* name; R multi, single; } routes[] = {
+        { "m.png", R::HostImage, R::HostImage }, { "m.PPM", R::HostImage, R::HostImage }, { "m.jpg", R::DeviceJpeg, R::HostImage }, { "m.JPEG", R::DeviceJpeg, R::HostImage },
+        { "m.tif", R::DeviceTiff, R::HostTiffGeo }, { "m.TIFF", R::DeviceTiff, R::HostTiffGeo }, { "mosaic", R::HostImage, R::HostImage },
+        { "dir.tif/m", R::HostImage, R::HostImage }, { ".jpg", R::DeviceJpeg, R::HostImage }, { "tif", R::HostImage, R::HostImage }, { "", R::HostImage, R::HostImage },
+    };
+    for (auto& r : routes)
+        if (pf::save_route(r.name, false) != r.multi || pf::save_route(r.name, true) != r.single) { std::printf("MISMATCH route of \"%s\"\n", r.name); fails++; }
+    if (pf::tiff_route(false) != R::DeviceTiff || pf::tiff_route(true) != R::HostTiffGeo || !pf::route_on_device(R::DeviceJpeg) || !pf::route_on_device(R::DeviceTiff) ||
+        pf::route_on_device(R::HostTiffGeo) || pf::route_on_device(R::HostImage)) { std::printf("MISMATCH tiff_route / route_on_device\n"); fails++; }
     std::printf("files %d fails %d\n", files, fails);
     return fails ? 1 : 0;
 }

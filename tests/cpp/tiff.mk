@@ -4,7 +4,7 @@ CXX   ?= g++
 ROOT  := ../..
 SRC   := $(ROOT)/pi-slam-fusion_amd/csrc
 HOST  := $(SRC)/jpeg_decode.cpp $(SRC)/png_decode.cpp $(SRC)/image_io.cpp
-HDRS  := $(SRC)/jpeg_decode.hpp $(SRC)/jpeg_encode.hpp $(SRC)/tiff_pyramid.hpp $(ROOT)/include/pifusion.h
+HDRS  := $(SRC)/image_io.hpp $(SRC)/jpeg_decode.hpp $(SRC)/jpeg_encode.hpp $(SRC)/tiff_pyramid.hpp $(ROOT)/include/pifusion.h
 FLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall -I$(SRC) -I$(ROOT)/include
 OUT   ?= build
 

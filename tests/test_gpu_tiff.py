@@ -203,3 +203,78 @@ def test_dist_save_tif_on_rank_0_equals_the_unsharded_file(pf, orc, tmp_path):
         d.close()
     for m in maps + [whole]:
         m.close()
+
+
+def test_failed_save_tiff_leaves_nothing_behind_for_the_next_save(pf, orc, tmp_path):
+    """the quality and the BigTIFF flag travel with the call: a save_tiff that fails cannot turn the next save into a TIFF"""
+    g, _ = build_map(pf, orc, 0, 5)
+    assert not g.save_tiff(str(tmp_path / "missing" / "x.tif"), 80, True)
+    f = str(tmp_path / "x.jpg")
+    assert g.save(f) and open(f, "rb").read(2) == b"\xff\xd8"
+    g.close()
+
+
+def test_save_tiff_and_save_jpg_from_two_threads_keep_their_formats(pf, orc, tmp_path):
+    """one map, two callers: each file is what its own call asked for, every time (8 calls each, no more)"""
+    import threading
+    g, _ = build_map(pf, orc, 0, 5)
+    a, b = str(tmp_path / "a.tif"), str(tmp_path / "b.jpg")
+    seen = {"a": [], "b": []}
+
+    def tiffs():
+        for _ in range(8):
+            seen["a"].append((g.save_tiff(a, 80), open(a, "rb").read(4)))
+
+    def jpegs():
+        for _ in range(8):
+            seen["b"].append((g.save(b), open(b, "rb").read(2)))
+
+    th = [threading.Thread(target=tiffs), threading.Thread(target=jpegs)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(120)
+    assert not any(t.is_alive() for t in th)
+    assert seen["a"] == [(True, b"II*\x00")] * 8
+    assert seen["b"] == [(True, b"\xff\xd8")] * 8
+    g.close()
+
+
+def test_save_while_the_worker_grows_the_grid(pf, tmp_path):
+    """thread = True: keyframes that add tiles outside the old bounding box are rendered between the saves of another thread; each save
+    sizes its picture and fills it under one hold of the map, so every file is a whole mosaic of some moment"""
+    import ctypes as C
+    import threading
+    wl = workloads()
+    cam = [640, 480, 500, 500, 320, 240]
+    poses = jitter_poses(10, seed=21, step=(70.0, 45.0))
+    g = pf.Map2D.create(pf.TypeMultiBandCPU, True)
+    assert g.prepare(wl.IDENTITY_PLANE, cam, poses[:2])
+    assert g.feed(wl.smooth_frame(480, 640, 0), poses[0]) and g.sync()
+    before = g.save_to_memory()[0].shape
+    fed, saved = [], []
+    f = str(tmp_path / "x.png")
+
+    def feeder():
+        for k, p in enumerate(poses[1:], 1):
+            fed.append(g.feed(wl.smooth_frame(480, 640, k), p))
+
+    def saver():
+        for _ in range(4):
+            ok = g.save(f)
+            r, c = C.c_int(), C.c_int()
+            saved.append((ok, pf.lib().pf_image_info(f.encode(), C.byref(r), C.byref(c)), r.value, c.value))
+
+    th = [threading.Thread(target=feeder), threading.Thread(target=saver)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(120)
+    assert not any(t.is_alive() for t in th)
+    assert len(fed) == len(poses) - 1 and len(saved) == 4
+    for ok, info, r, c in saved:
+        assert ok and info == 1 and r > 0 and c > 0 and r % 256 == 0 and c % 256 == 0, saved
+    assert g.sync()
+    after = g.save_to_memory()[0].shape
+    assert after[0] * after[1] > before[0] * before[1]                    # the sequence did grow the mosaic
+    g.close()
