@@ -473,6 +473,9 @@ bool FusionMap::upload(const pf_image* img, int slot)
     return true;
 }
 
+// the line renderFrame's size / type gate prints (.cpp:319-323)
+static void print_frame_mismatch() { std::fprintf(stderr, "MultiBandMap2DCPU::renderFrame: frame.first.cols!=p->_camera.w||frame.first.rows!=p->_camera.h||frame.first.type()!=CV_8UC3\n"); }
+
 // MultiBandMap2DCPU::feed (.cpp:288-309)
 bool FusionMap::feed(const pf_image* img, const double pose7[7], bool device_ptr, const FrameProducer* produce)
 {
@@ -490,8 +493,8 @@ bool FusionMap::feed(const pf_image* img, const double pose7[7], bool device_ptr
             // wrong size/type is reported by renderFrame (.cpp:319-323); keep that order of checks
             f.rows = img->rows; f.cols = img->cols;
             f.cn = img->type == PF_8UC4 ? 4 : 3;     // BGRA frames are accepted as the tracker produces them (row f1)
-            if ((img->type != PF_8UC3 && img->type != PF_8UC4) || img->cols != cam_.w || img->rows != cam_.h) {
-                std::fprintf(stderr, "MultiBandMap2DCPU::renderFrame: frame.first.cols!=p->_camera.w||frame.first.rows!=p->_camera.h||frame.first.type()!=CV_8UC3\n");
+            if (frame_mismatch(img->type, img->cols, img->rows)) {
+                print_frame_mismatch();
                 if (!thread_) { n_rejected_++; return false; }
                 return true;    // the threaded reference enqueues and fails later on the render thread
             }
@@ -552,17 +555,10 @@ bool FusionMap::frame_needs(const double pose7[7], std::vector<unsigned char>& r
     const Pose pose = mul(plane_inv_, pose_from7(pose7));
     double pts[8];
     if (!footprint(cam_, pose, pts)) return true;            // oblique view: nobody renders it (feed will say false)
-    double xmin = pts[0], xmax = xmin, ymin = pts[1], ymax = ymin;
-    for (int i = 1; i < 4; i++) {
-        xmin = std::min(xmin, pts[2 * i]); xmax = std::max(xmax, pts[2 * i]);
-        ymin = std::min(ymin, pts[2 * i + 1]); ymax = std::max(ymax, pts[2 * i + 1]);
-    }
-    if (xmin < min_[0] || xmax > max_[0] || ymin < min_[1] || ymax > max_[1])
-        if (!spread_map(xmin, ymin, xmax, ymax)) return false;
-    const int x0 = (int)std::floor((xmin - min_[0]) * ele_size_inv_), y0 = (int)std::floor((ymin - min_[1]) * ele_size_inv_);
-    const int x1 = (int)std::ceil((xmax - min_[0]) * ele_size_inv_), y1 = (int)std::ceil((ymax - min_[1]) * ele_size_inv_);
-    for (int y = y0; y < y1; y++)
-        for (int x = x0; x < x1; x++)
+    Win r;
+    if (!canvas_range(pts, r)) return false;
+    for (int y = r.y0; y < r.y1; y++)
+        for (int x = r.x0; x < r.x1; x++)
             rank_needs[(size_t)tile_owner(opt_.shard_count, opt_.shard_block, x + off_x_, y + off_y_)] = 1;
     return true;
 }
@@ -573,8 +569,8 @@ bool FusionMap::reject_mismatched_frame(const pf_image* desc)
 {
     std::lock_guard<std::mutex> l(mu_);
     if (!valid_) return false;
-    if ((desc->type != PF_8UC3 && desc->type != PF_8UC4) || desc->cols != cam_.w || desc->rows != cam_.h) {
-        std::fprintf(stderr, "MultiBandMap2DCPU::renderFrame: frame.first.cols!=p->_camera.w||frame.first.rows!=p->_camera.h||frame.first.type()!=CV_8UC3\n");
+    if (frame_mismatch(desc->type, desc->cols, desc->rows)) {
+        print_frame_mismatch();
         n_rejected_++;
         return true;
     }
@@ -587,7 +583,7 @@ int FusionMap::stage_frame(const pf_image* desc, bool upload_host, void** dev, s
     if (!init_ok_ || !valid_ || !set_device() || thread_) { set_error("stage_frame: needs a prepared thread=0 map"); return -1; }
     const int cn = desc->type == PF_8UC4 ? 4 : 3;
     const size_t row = (size_t)desc->cols * cn, step = desc->step ? desc->step : row;
-    if ((desc->type != PF_8UC3 && desc->type != PF_8UC4) || desc->cols != cam_.w || desc->rows != cam_.h || step < row ||
+    if (frame_mismatch(desc->type, desc->cols, desc->rows) || step < row ||
         step * (size_t)desc->rows >= (1ull << 31)) { set_error("stage_frame: frame does not match the camera"); return -1; }
     const int slot = acquire_slot((size_t)desc->rows * step);
     if (slot < 0) return -1;
@@ -671,17 +667,40 @@ bool FusionMap::sync()
     return true;
 }
 
+// the tiles (dense index) a box of plane coordinates touches
+void FusionMap::tile_range(double xmin, double ymin, double xmax, double ymax, Win& r) const
+{
+    r.x0 = (int)std::floor((xmin - min_[0]) * ele_size_inv_);
+    r.y0 = (int)std::floor((ymin - min_[1]) * ele_size_inv_);
+    r.x1 = (int)std::ceil((xmax - min_[0]) * ele_size_inv_);
+    r.y1 = (int)std::ceil((ymax - min_[1]) * ele_size_inv_);
+}
+
+// 2. destination tile range of a footprint, spreadMap when it leaves the grid (.cpp:349-394)
+bool FusionMap::canvas_range(const double pts[8], Win& r)
+{
+    double xmin = pts[0], xmax = xmin, ymin = pts[1], ymax = ymin;
+    for (int i = 1; i < 4; i++) {
+        if (pts[2 * i] < xmin) xmin = pts[2 * i];
+        if (pts[2 * i + 1] < ymin) ymin = pts[2 * i + 1];
+        if (pts[2 * i] > xmax) xmax = pts[2 * i];
+        if (pts[2 * i + 1] > ymax) ymax = pts[2 * i + 1];
+    }
+    if (xmin < min_[0] || xmax > max_[0] || ymin < min_[1] || ymax > max_[1])
+        if (!spread_map(xmin, ymin, xmax, ymax)) return false;
+    tile_range(xmin, ymin, xmax, ymax, r);
+    return true;
+}
+
 // spreadMap (.cpp:561-604): geometry only -- tiles live in a hash keyed by
 // stable coordinates, so nothing is re-laid out.
 bool FusionMap::spread_map(double xmin, double ymin, double xmax, double ymax)
 {
     Section sec(this, T_SPREAD);
-    int xminInt = (int)std::floor((xmin - min_[0]) * ele_size_inv_);
-    int yminInt = (int)std::floor((ymin - min_[1]) * ele_size_inv_);
-    int xmaxInt = (int)std::ceil((xmax - min_[0]) * ele_size_inv_);
-    int ymaxInt = (int)std::ceil((ymax - min_[1]) * ele_size_inv_);
-    xminInt = std::min(xminInt, 0); yminInt = std::min(yminInt, 0);
-    xmaxInt = std::max(xmaxInt, w_); ymaxInt = std::max(ymaxInt, h_);
+    Win r;
+    tile_range(xmin, ymin, xmax, ymax, r);
+    const int xminInt = std::min(r.x0, 0), yminInt = std::min(r.y0, 0);
+    const int xmaxInt = std::max(r.x1, w_), ymaxInt = std::max(r.y1, h_);
     const int w = xmaxInt - xminInt, h = ymaxInt - yminInt;
     const double mnx = min_[0] + ele_size_ * xminInt, mny = min_[1] + ele_size_ * yminInt;
     const double mxx = mnx + w * ele_size_, mxy = mny + h * ele_size_;
@@ -692,19 +711,14 @@ bool FusionMap::spread_map(double xmin, double ymin, double xmax, double ymax)
 
 // ------------------------------------------------------------ renderFrame
 // MultiBandMap2DCPU::renderFrame (.cpp:311-558) in stages; FrameWork (fusion_map.hpp) is what one stage leaves for the next:
-//   frame_canvas        1-3  footprint, tile range, homography                         (.cpp:324-441)
+//   frame_canvas        1-3  footprint, tile range (canvas_range), homography          (.cpp:324-441)
 //   build_tile_table         Apply's tile loop: owned tiles, the cull, the table entries (.cpp:476-492)
-//   level_windows / plan_fused_levels   where each pyramid level is needed: windows, compute regions, need bitmaps and rectangles
+//   LevelPlan::windows / plan_fused_levels   where each pyramid level is needed: windows, compute regions, need bitmaps and rectangles
+// The arithmetic of the plan -- the cull's bounds (Lattice) and the levels (LevelPlan) -- is frame_plan.hpp: pure, and checked on the CPU
+// (tests/cpp/frame_plan_check.cpp).  Here: tiles, counters, the profiler and the launches around it.
 //   reserve_frame_workspace / place_table   grow-only buffers, the table's ring slot
 //   launch_fused_pipeline | launch_level_streams | launch_per_op | launch_single_band   the kernels (.cpp:443-555)
 //   retire_frame             flags, weight bounds, counters
-namespace {
-inline void clampw(int lo, int hi, int n, int& o0, int& o1) { o0 = std::max(lo, 0); o1 = std::min(hi, n); }
-// a box of level-0 pixels (multiples of 64) at level i: floor / ceil (at the top levels a cell is less than a pixel)
-inline int lv_lo(int p, int i) { return p >> i; }
-inline int lv_hi(int p, int i) { return (p + (1 << i) - 1) >> i; }
-}
-
 bool FusionMap::render_frame(const QueuedFrame& f)
 {
     Section sec(this, T_RENDER);
@@ -727,7 +741,8 @@ bool FusionMap::render_frame(const QueuedFrame& f)
     if (f.slot >= 0) { std::lock_guard<std::mutex> q(qmu_); slots_[f.slot].queued = true; }      // held until the keyframe is rendered (retire_frame)
     size_t keep = 0;
     if (w.cull) {
-        if (lat_.sx.capacity() == 0 && !lat_pool_.empty()) { lat_ = std::move(lat_pool_.back()); lat_pool_.pop_back(); }
+        if (!lat_pool_.empty()) { p.lat = std::move(lat_pool_.back()); lat_pool_.pop_back(); }
+        w.lat = &p.lat;
         // a shard that owns a quarter of the canvas' tiles or more has the whole lattice mapped at once, like an unsharded map (one tile_owner
         // call per tile: ~1 us); below that the points are mapped as its tiles ask for them
         bool map_all = opt_.shard_count <= 1;
@@ -737,7 +752,7 @@ bool FusionMap::render_frame(const QueuedFrame& f)
                 for (int x = 0; x < w.tx; x++) mine += tile_owner(opt_.shard_count, opt_.shard_block, w.xminInt + x + off_x_, w.yminInt + y + off_y_) == opt_.shard_rank;
             map_all = 4 * mine >= w.tx * w.ty;
         }
-        cull_lattice(w.Minv, w.crows, w.ccols, f.cols, f.rows, single_band_ ? 0 : ((2 << w.L) - 2 + 63) / 64, map_all);
+        p.lat.map_canvas(w.Minv, w.crows, w.ccols, f.cols, f.rows, single_band_ ? 0 : ((2 << w.L) - 2 + 63) / 64, map_all, cull_margins_);
         if (lookahead_ok()) {
             // the keyframe's own lower bounds enter the tiles' wlb NOW: the keyframes ahead of it in the queue are decided against them
             if (!tiles_pool_.empty()) { p.tiles = std::move(tiles_pool_.back()); tiles_pool_.pop_back(); }
@@ -746,7 +761,6 @@ bool FusionMap::render_frame(const QueuedFrame& f)
             since_drain_++;
             keep = std::min<size_t>((size_t)opt_.lookahead, 2 * (size_t)since_drain_ / 3);
         }
-        std::swap(lat_, p.lat);
     }
     // a keyframe that cannot take part (no cull for it: an untame homography, a per-level or per-op map, the cull switched off) is rendered at
     // once, and everything that waits before it; a failure of one of THOSE renders is reported by this call
@@ -755,52 +769,12 @@ bool FusionMap::render_frame(const QueuedFrame& f)
     return true;
 }
 
-// The weight bounds of an admitted keyframe go into its tiles' wlb (which only ever rises; build_tile_table does not work them out again).
-// Creates the canvas' tiles, as Apply's tile loop does (.cpp:478-492), and remembers them for the render.  A keyframe never culls
-// itself by this: the largest weight it can have in a cell is not below the smallest (cell_out's margins only widen the gap).
+// The weight bounds of an admitted keyframe go into its tiles' wlb (Lattice::raise_bounds; build_tile_table does not work them out again).
+// Creates the canvas' tiles, as Apply's tile loop does (.cpp:478-492), and remembers them for the render.
 void FusionMap::pre_raise(FrameWork& w, std::vector<Tile*>& tiles)
 {
     tiles.assign((size_t)w.tx * w.ty, nullptr);
-
-    const int S = cull_sub_, span = 4 / S;
     const bool sharded = opt_.shard_count > 1;
-    if (lat_.all && S == 4) {
-        // Every lattice point is mapped (cull_lattice), every cell of an owned tile is asked.  The same arithmetic as cell_out's first half, without
-        // its calls: the farthest corner of a cell's dilated square from a pass that pairs the points e steps apart along a row first.
-        const int nx = lat_.nx, ny = lat_.ny, e = 1 + 2 * lat_.dil;
-        pair_d_.resize((size_t)nx * ny); pair_in_.resize((size_t)nx * ny);
-        for (int m = 0; m < ny; m++) {
-            const double* __restrict__ d = lat_.d.data() + (size_t)m * nx; const unsigned char* __restrict__ in = lat_.in.data() + (size_t)m * nx;
-            double* __restrict__ pd = pair_d_.data() + (size_t)m * nx; unsigned char* __restrict__ pi = pair_in_.data() + (size_t)m * nx;
-            for (int k = 0; k + e < nx; k++) { pd[k] = std::max(d[k], d[k + e]); pi[k] = in[k] & in[k + e]; }
-        }
-        const double mpx = cull_margin_px_, mw = cull_margin_w_;
-        const int wt = opt_.weight_type;
-        for (int y = 0; y < w.ty; y++)
-            for (int x = 0; x < w.tx; x++) {
-                const int sx = w.xminInt + x + off_x_, sy = w.yminInt + y + off_y_;
-                if (sharded && tile_owner(opt_.shard_count, opt_.shard_block, sx, sy) != opt_.shard_rank) continue;
-                Tile* t = store_.get_or_create(sx, sy);
-                if (!t) { tiles.clear(); return; }
-                tiles[(size_t)y * w.tx + x] = t;
-                for (int qy = 0; qy < 4; qy++) {
-                    const size_t r0 = (size_t)(4 * y + qy) * nx + 4 * x, r1 = r0 + (size_t)e * nx;
-                    for (int qx = 0; qx < 4; qx++) {
-                        if (!(pair_in_[r0 + qx] & pair_in_[r1 + qx])) continue;              // not wholly inside the frame: wmin 0
-                        float& wl = t->wlb[4 * qy + qx];
-                        const double far2 = std::max(pair_d_[r0 + qx], pair_d_[r1 + qx]);
-                        const double tw = wt == 0 ? (1.0 - mw - (double)wl) * lat_.dis_max - mpx : 1e300;
-                        if (!(tw > 0 && far2 < tw * tw * (1.0 + 1e-9))) continue;
-                        const double dfar = std::sqrt(far2) + mpx;
-                        double ww = 1.0 - dfar * lat_.inv_dis_max;
-                        if (wt != 0) ww = ww > 0 ? ww * ww : 0.0;
-                        ww -= mw;
-                        if (ww > 2e-5 && (float)ww > wl) wl = (float)ww;
-                    }
-                }
-            }
-        return;
-    }
     for (int y = 0; y < w.ty; y++)
         for (int x = 0; x < w.tx; x++) {
             const int sx = w.xminInt + x + off_x_, sy = w.yminInt + y + off_y_;
@@ -808,11 +782,7 @@ void FusionMap::pre_raise(FrameWork& w, std::vector<Tile*>& tiles)
             Tile* t = store_.get_or_create(sx, sy);
             if (!t) { tiles.clear(); return; }                // HBM exhausted: build_tile_table meets it again and reports it
             tiles[(size_t)y * w.tx + x] = t;                  // (references into the store stay valid while it grows)
-            for (int q = 0; q < S * S; q++) {
-                float wmin;
-                (void)cell_out(4 * x + span * (q % S), 4 * y + span * (q / S), span, opt_.weight_type, t->wlb[q], false, &wmin);
-                if (wmin > t->wlb[q]) t->wlb[q] = wmin;
-            }
+            w.lat->raise_bounds(x, y, opt_.weight_type, t->wlb);
         }
 }
 
@@ -836,7 +806,7 @@ bool FusionMap::drain()
 // stages 4 onwards of renderFrame for the oldest keyframe that waits
 bool FusionMap::render_front()
 {
-    struct Pop {            // the keyframe leaves the queue whatever happens to it (its lattice stays in lat_: the next admission writes over it)
+    struct Pop {            // the keyframe leaves the queue whatever happens to it (its lattice's buffers go back to the pool)
         FusionMap* m;
         ~Pop() {
             PendingFrame& p = m->pending_.front();
@@ -858,7 +828,7 @@ bool FusionMap::render_front()
     w.pre_raised = p.pre_raised;
     w.tiles_known = p.tiles.size() == (size_t)p.tx * p.ty ? p.tiles.data() : nullptr;
     w.src = f.ext ? f.ext : slots_[f.slot].dev;
-    if (p.cull) std::swap(lat_, p.lat);
+    w.lat = &p.lat;
     Section sec_apply(this, T_APPLY);          // the reference times its tile loop under this name (.cpp:476-555); here: table, need rectangles, launch
     if (!build_tile_table(f, w)) return false;
     if (w.bx0 >= w.bx1) {                      // nothing of this frame lands on this shard, or it cannot win anywhere it lands
@@ -870,7 +840,7 @@ bool FusionMap::render_front()
     }
     px_owned_ += (double)w.owned * kElePixels * kElePixels;     // what this rank renders beyond its share: owned tile pixels vs the level-0 window (bench --shard strong)
     n_with_pixels_++;
-    level_windows(w);
+    w.plan.windows(w.pb, w.L, w.crows, w.ccols);
     if (!reserve_frame_workspace(w) || !place_table(w)) return false;
     warp_args(f, w);
     const bool fused = opt_.fused != 0 && w.L >= 1;
@@ -907,25 +877,14 @@ int FusionMap::frame_canvas(const QueuedFrame& f, FrameWork& w)
 {
     double* pts = w.pts;
     if (!footprint(cam_, f.pose, pts)) return -1;
-    double xmin = pts[0], xmax = xmin, ymin = pts[1], ymax = ymin;
-    for (int i = 1; i < 4; i++) {
-        if (pts[2 * i] < xmin) xmin = pts[2 * i];
-        if (pts[2 * i + 1] < ymin) ymin = pts[2 * i + 1];
-        if (pts[2 * i] > xmax) xmax = pts[2 * i];
-        if (pts[2 * i + 1] > ymax) ymax = pts[2 * i + 1];
-    }
-    if (xmin < min_[0] || xmax > max_[0] || ymin < min_[1] || ymax > max_[1])
-        if (!spread_map(xmin, ymin, xmax, ymax)) return -1;
-    w.xminInt = (int)std::floor((xmin - min_[0]) * ele_size_inv_);
-    w.yminInt = (int)std::floor((ymin - min_[1]) * ele_size_inv_);
-    w.xmaxInt = (int)std::ceil((xmax - min_[0]) * ele_size_inv_);
-    w.ymaxInt = (int)std::ceil((ymax - min_[1]) * ele_size_inv_);
+    Win r;
+    if (!canvas_range(pts, r)) return -1;
+    w.xminInt = r.x0; w.yminInt = r.y0; w.xmaxInt = r.x1; w.ymaxInt = r.y1;
     if (w.xminInt < 0 || w.yminInt < 0 || w.xmaxInt > w_ || w.ymaxInt > h_ || w.xminInt >= w.xmaxInt || w.yminInt >= w.ymaxInt) {
         std::fprintf(stderr, "MultiBandMap2DCPU::renderFrame:should never happen!\n");
         return -1;
     }
-    xmin = min_[0] + ele_size_ * w.xminInt;
-    ymin = min_[1] + ele_size_ * w.yminInt;
+    const double xmin = min_[0] + ele_size_ * w.xminInt, ymin = min_[1] + ele_size_ * w.yminInt;
     w.src = f.ext ? f.ext : (f.slot >= 0 ? slots_[f.slot].dev : nullptr);
     if (!w.src) return 0;
     const float src4[8] = { 0.f, 0.f, (float)cam_.w, 0.f, 0.f, (float)cam_.h, (float)cam_.w, (float)cam_.h };
@@ -964,15 +923,9 @@ bool FusionMap::build_tile_table(const QueuedFrame& f, FrameWork& w)
     const int tx = w.tx, ty = w.ty;
     w.sharded = opt_.shard_count > 1;
     const bool sharded = w.sharded;
-    const bool cull = w.cull;                                    // decided when the keyframe was admitted (render_frame), with its lattice (lat_)
+    const bool cull = w.cull;                                    // decided when the keyframe was admitted (render_frame), with its lattice (w.lat)
     const bool lookahead = cull && lookahead_ok();
-    const int S = cull_sub_, span = 4 / S;                       // cells per tile edge; lattice steps per cell
-    if (cull) w.raise.reserve((size_t)tx * ty * S * S);
-    // Map2DCPU (single band, round 6): no pyramid, so a cell is not dilated; the bounds are those of the radial weight all the same, compared
-    // three alpha steps apart -- the stored alpha byte is floor(254 w) (at least 2) interpolated with 15-bit taps (within 1 of its smallest
-    // tap), the select is `ele.a < dst.a` (Map2DCPU.cpp:326-327): the keyframe cannot win where 254 wmax <= 254 wlb - 3.
-    const float sb_gap = single_band_ ? 3.2f / 254.f : 0.f, sb_floor = single_band_ ? 6.f / 254.f : 0.f;
-    auto stored_bound = [&](float wlb) { return wlb > sb_floor ? wlb - sb_gap : 0.f; };      // what cell_out compares the keyframe's weights with
+    if (cull) w.raise.reserve((size_t)tx * ty * cull_margins_.sub * cull_margins_.sub);
     const int B = opt_.shard_block;
     // cells of the need rectangles: a shard's hash cells; for the cull alone squares of 8 x 8 tiles as well (experiments library: PF_CULL_CELL)
     static const int bc_env = exp_env_int("PF_CULL_CELL", 0);
@@ -981,20 +934,10 @@ bool FusionMap::build_tile_table(const QueuedFrame& f, FrameWork& w)
     w.touched.reserve((size_t)tx * ty);
     w.bx0 = tx; w.bx1 = 0; w.by0 = ty; w.by1 = 0;
     // the same box in level-0 pixels, around the cells that are rendered (== the tiles' box when nothing is culled); the squares of the rectangles likewise
-    w.pbx0 = 1 << 30; w.pbx1 = 0; w.pby0 = 1 << 30; w.pby1 = 0;
+    w.pb = Win{ 1 << 30, 0, 1 << 30, 0 };
     auto add_rect = [&](int sx, int sy, int x0, int y0, int x1, int y1) {
-        w.pbx0 = std::min(w.pbx0, x0); w.pbx1 = std::max(w.pbx1, x1); w.pby0 = std::min(w.pby0, y0); w.pby1 = std::max(w.pby1, y1);
-        if (!(sharded || cull) || w.cells_overflow) return;
-        const int cx = floordiv(sx, Bc), cy = floordiv(sy, Bc);
-        int k = w.ncells - 1;
-        while (k >= 0 && !(w.cells[k].cx == cx && w.cells[k].cy == cy)) k--;
-        if (k < 0) {
-            if (w.ncells == 64) w.cells_overflow = true;
-            else w.cells[w.ncells++] = FrameWork::Cell{ cx, cy, x0, y0, x1, y1 };
-        } else {
-            FrameWork::Cell& c = w.cells[k];
-            c.x0 = std::min(c.x0, x0); c.y0 = std::min(c.y0, y0); c.x1 = std::max(c.x1, x1); c.y1 = std::max(c.y1, y1);
-        }
+        w.pb.x0 = std::min(w.pb.x0, x0); w.pb.x1 = std::max(w.pb.x1, x1); w.pb.y0 = std::min(w.pb.y0, y0); w.pb.y1 = std::max(w.pb.y1, y1);
+        if (sharded || cull) w.cells.add(floordiv(sx, Bc), floordiv(sy, Bc), x0, y0, x1, y1);
     };
     for (int y = 0; y < ty; y++) {
         const int sy = w.yminInt + y + off_y_;
@@ -1008,30 +951,11 @@ bool FusionMap::build_tile_table(const QueuedFrame& f, FrameWork& w)
                 w.owned_all++;
                 unsigned out = 0;                                  // 64 x 64 cells in which this keyframe cannot win (bit 4 * row + column)
                 if (cull) {
-                    // the whole tile first, against the smallest of its cells' bounds: out there is out in every cell (the tile's dilated
-                    // rectangle holds each cell's) -- most culled cells lie in such tiles; without lookahead their wmin is still worked out
-                    // cell by cell, with it the bounds went into wlb when the keyframe was admitted (pre_raise) and the cells are skipped
-                    // A FRESH tile (no keyframe has written it: its first one copies unconditionally, .cpp:498) is rendered whole or not at
-                    // all: its slot holds no weights a select could be run against, so no single cell may be left out.  It can be left out
-                    // whole only through the lookahead -- its wlb then holds bounds of keyframes that wait behind this one; the one whose
-                    // bound is the largest in a cell is never out there and renders the tile (all of it) before anybody looks.  Without
-                    // lookahead a fresh tile's wlb is -1 and nothing is out.
-                    bool tile_out = false;
-                    const bool ask = !t->fresh || lookahead;
-                    if (ask) {
-                        float wl = t->wlb[0], unused;
-                        for (int q = 1; q < S * S; q++) wl = std::min(wl, t->wlb[q]);
-                        tile_out = cell_out(4 * x, 4 * y, 4, opt_.weight_type, stored_bound(wl), true, &unused);
-                    }
-                    if (tile_out && w.pre_raised) out = 0xffffu;       // (the keyframe's own bounds are in wlb since it was admitted)
-                    else for (int q = 0; q < S * S; q++) {
-                        const int qx = q % S, qy = q / S;
-                        float wmin = 0.f;
-                        if (cell_out(4 * x + span * qx, 4 * y + span * qy, span, opt_.weight_type, stored_bound(t->wlb[q]), ask && !tile_out, w.pre_raised ? nullptr : &wmin) || tile_out)
-                            out |= S == 4 ? 1u << q : 0x33u << (8 * qy + 2 * qx);
-                        if (wmin > t->wlb[q]) w.raise.push_back(FrameWork::Raise{ t, q, wmin });
-                    }
-                    if (t->fresh && out != 0xffffu) out = 0;
+                    // the whole tile, then cell by cell; a fresh tile is rendered whole or not at all (Lattice::tile_cull)
+                    TileCull c;
+                    w.lat->tile_cull(x, y, t->wlb, t->fresh, lookahead, w.pre_raised, opt_.weight_type, single_band_, c);
+                    out = c.out;
+                    for (int k = 0; k < c.nraise; k++) w.raise.push_back(FrameWork::Raise{ t, c.q[k], c.w[k] });
                     if (out == 0xffffu && t->fresh) {
                         // stays fresh, and is not yet a tile of the mosaic (no Ischanged: it has no pyramid, .cpp:717-718)
                         w.culled_any = true; table_tmp_[(size_t)y * tx + x] = 0; n_culled_tiles_++;
@@ -1063,27 +987,6 @@ bool FusionMap::build_tile_table(const QueuedFrame& f, FrameWork& w)
         }
     }
     return true;
-}
-
-// per-level windows: Gaussian level i must be valid on need[i] so that the
-// Laplacian of the owned tiles is exact (pyrDown reads [2p-2, 2q+1), pyrUp +-1)
-void FusionMap::level_windows(FrameWork& w)
-{
-    const int L = w.L;
-    for (int i = L; i >= 0; i--) {
-        const int rows = w.crows >> i, cols = w.ccols >> i;
-        int x0 = lv_lo(w.pbx0, i), x1 = lv_hi(w.pbx1, i), y0 = lv_lo(w.pby0, i), y1 = lv_hi(w.pby1, i);
-        if (i > 0) { x0 -= 1; x1 += 1; y0 -= 1; y1 += 1; }
-        if (i < L) {
-            x0 = std::min(x0, 2 * w.need[i + 1].x0 - 2); x1 = std::max(x1, 2 * w.need[i + 1].x1 + 1);
-            y0 = std::min(y0, 2 * w.need[i + 1].y0 - 2); y1 = std::max(y1, 2 * w.need[i + 1].y1 + 1);
-        }
-        clampw(x0, x1, cols, w.need[i].x0, w.need[i].x1);
-        clampw(y0, y1, rows, w.need[i].y0, w.need[i].y1);
-    }
-    // level 0 is produced by the warp in 64x4 blocks
-    w.need[0].x0 = (w.need[0].x0 / 64) * 64; w.need[0].x1 = std::min(w.ccols, ((w.need[0].x1 + 63) / 64) * 64);
-    w.need[0].y0 = (w.need[0].y0 / 4) * 4;   w.need[0].y1 = std::min(w.crows, ((w.need[0].y1 + 3) / 4) * 4);
 }
 
 // grow-only workspace: per-frame Gaussian levels (GW_i of the fused forms, G_i / W_i of the per-op form) and the tile-table ring
@@ -1148,7 +1051,8 @@ void FusionMap::warp_args(const QueuedFrame& f, FrameWork& w)
     if (!invert3x3(w.M0, a.M)) std::memset(a.M, 0, sizeof(a.M));
     a.srows = f.rows; a.scols = f.cols; a.sstep = f.step;
     a.crows = w.crows; a.ccols = w.ccols;
-    a.y_off = w.need[0].y0; a.x_off = w.need[0].x0; a.wrows = w.need[0].y1 - w.need[0].y0; a.wcols = w.need[0].x1 - w.need[0].x0;
+    const Win& n0 = w.plan.need[0];
+    a.y_off = n0.y0; a.x_off = n0.x0; a.wrows = n0.y1 - n0.y0; a.wcols = n0.x1 - n0.x0;
     a.xc = (float)(f.cols / 2); a.yc = (float)(f.rows / 2);
     a.dis_max = std::sqrt(a.xc * a.xc + a.yc * a.yc);
     a.weight_type = opt_.weight_type;
@@ -1173,196 +1077,19 @@ bool FusionMap::launch_single_band(const QueuedFrame& f, FrameWork& w)
     return true;
 }
 
-// Fused forms: where the level kernels run.
-//   C[i]         compute region of level i: its launch must cover the owned tiles and produce GW_{i+1} wherever the level i+1
-//                launch stages its halo (its region -4 / +3)
-//   need bitmaps upper levels: one bit per block of the level's grid -- does a rendered cell lie within the pyramid's reach of it (the
-//                rule the level-0 blocks apply to themselves in the kernel: (3 * 2^(L-i) - 2) level-i pixels)?  From row bitmaps of the
-//                rendered cells (canvases up to 32 tiles wide); the jobs carry them in their launches' kernel arguments
-//   rectangles   a shard's tiles are scattered hash cells, and the compute regions are their bounding box: per level, one rectangle of
-//                64x32 blocks per cell says where something owned depends on a block (the same recursion as `need`, applied per
-//                cell); blocks outside every rectangle exit at once.  The fallback of the bitmaps.  (Unsharded, no cull: every block runs.)
+// Fused forms: where the level kernels run (LevelPlan, frame_plan.hpp), and the level-0 pixels that costs (render_stats)
 void FusionMap::plan_fused_levels(FrameWork& w)
 {
-    const int L = w.L, tx = w.tx, ty = w.ty, crows = w.crows, ccols = w.ccols;
-    Win* C = w.C;
-    for (int i = L - 1; i >= 0; i--) {
-        const int rows = crows >> i, cols = ccols >> i;
-        // the origin stays even (a block's quads and its part of level i+1 start on even pixels): a box of 64-pixel cells is odd at level 6
-        int x0 = lv_lo(w.pbx0, i) & ~1, x1 = lv_hi(w.pbx1, i), y0 = lv_lo(w.pby0, i) & ~1, y1 = lv_hi(w.pby1, i);
-        if (i < L - 1) {
-            x0 = std::min(x0, 2 * (C[i + 1].x0 - 4)); x1 = std::max(x1, 2 * (C[i + 1].x1 + 3));
-            y0 = std::min(y0, 2 * (C[i + 1].y0 - 4)); y1 = std::max(y1, 2 * (C[i + 1].y1 + 3));
-        }
-        clampw(x0, x1, cols, C[i].x0, C[i].x1);
-        clampw(y0, y1, rows, C[i].y0, C[i].y1);
-    }
-    const bool partial = (w.sharded || w.culled_any) && !w.cells_overflow;
     const int BHr = level_block_rows(lay_.f32 != 0);
-    if (partial && 4 * tx <= 128 && L >= 2) {
-        typedef unsigned __int128 u128;
-        cell_rows_.assign((size_t)4 * ty, 0);
-        for (int y = 0; y < ty; y++)
-            for (int x = 0; x < tx; x++) {
-                const uint64_t e = table_tmp_[(size_t)y * tx + x];
-                if (!e) continue;
-                const unsigned in = ~(unsigned)(e >> 48) & 0xffffu;
-                for (int r = 0; r < 4; r++) cell_rows_[(size_t)4 * y + r] |= (u128)((in >> (4 * r)) & 15u) << (4 * x);
-            }
-        for (int i = 1; i < L; i++) {
-            const int reach = ((3 << (L - i)) - 2) << i, nbx = (C[i].x1 - C[i].x0 + 63) / 64, nby = (C[i].y1 - C[i].y0 + BHr - 1) / BHr;
-            w.need_n[i] = 0;
-            if (nbx <= 0 || nby <= 0 || (nbx * nby + 31) / 32 > kNeedWords) continue;
-            uint32_t* bits = need_tmp_[i];
-            std::memset(bits, 0, sizeof(uint32_t) * (size_t)((nbx * nby + 31) / 32));
-            for (int gy = 0; gy < nby; gy++) {
-                const int y0 = std::max(((C[i].y0 + gy * BHr) << i) - reach, 0) >> 6, y1 = std::min((((C[i].y0 + gy * BHr + BHr) << i) - 1 + reach) >> 6, 4 * ty - 1);
-                u128 rowsum = 0;
-                for (int r = y0; r <= y1; r++) rowsum |= cell_rows_[(size_t)r];
-                if (!rowsum) continue;
-                for (int gx = 0; gx < nbx; gx++) {
-                    const int x0 = std::max(((C[i].x0 + gx * 64) << i) - reach, 0) >> 6, x1 = std::min((((C[i].x0 + gx * 64 + 64) << i) - 1 + reach) >> 6, 4 * tx - 1);
-                    if (x0 > x1) continue;
-                    const u128 m = (x1 - x0 >= 127 ? ~(u128)0 : (((u128)1 << (x1 - x0 + 1)) - 1)) << x0;
-                    if (rowsum & m) { const int b = gy * nbx + gx; bits[(size_t)b >> 5] |= 1u << (b & 31); }
-                }
-            }
-            w.need_n[i] = nbx * nby;
-        }
-    }
-    if (!(partial && opt_.fused == 1)) {
-        px_level0_ += (double)(C[0].x1 - C[0].x0) * (C[0].y1 - C[0].y0);
-        return;
-    }
-    struct R { int x0, y0, x1, y1; };
-    std::vector<R> lv[kMaxLevels];
-    for (int c = 0; c < w.ncells; c++) {
-        // N[i]: where Gaussian level i is needed for this cell's tiles (pixel-exact: pyrDown reads [2p-2, 2p+2],
-        // pyrUp +-1).  The level-i block at b runs iff it holds owned pixels or its part of level i+1 lies in
-        // N[i+1]; what else it computes from unproduced input is never read.
-        const FrameWork::Cell& ce = w.cells[c];
-        Win N[kMaxLevels];
-        for (int i = L; i >= 0; i--) {
-            const int rows = crows >> i, cols = ccols >> i;
-            int x0 = lv_lo(ce.x0, i), x1 = lv_hi(ce.x1, i), y0 = lv_lo(ce.y0, i), y1 = lv_hi(ce.y1, i);
-            if (i > 0) { x0 -= 1; x1 += 1; y0 -= 1; y1 += 1; }
-            if (i < L) {
-                x0 = std::min(x0, 2 * N[i + 1].x0 - 2); x1 = std::max(x1, 2 * N[i + 1].x1 + 1);
-                y0 = std::min(y0, 2 * N[i + 1].y0 - 2); y1 = std::max(y1, 2 * N[i + 1].y1 + 1);
-            }
-            clampw(x0, x1, cols, N[i].x0, N[i].x1);
-            clampw(y0, y1, rows, N[i].y0, N[i].y1);
-        }
-        for (int i = 0; i < L; i++) {
-            int x0 = std::min(lv_lo(ce.x0, i), 2 * N[i + 1].x0), x1 = std::max(lv_hi(ce.x1, i), 2 * N[i + 1].x1);
-            int y0 = std::min(lv_lo(ce.y0, i), 2 * N[i + 1].y0), y1 = std::max(lv_hi(ce.y1, i), 2 * N[i + 1].y1);
-            x0 = std::max(x0, C[i].x0); y0 = std::max(y0, C[i].y0); x1 = std::min(x1, C[i].x1); y1 = std::min(y1, C[i].y1);
-            if (x0 >= x1 || y0 >= y1) continue;
-            lv[i].push_back(R{ (x0 - C[i].x0) / 64, (y0 - C[i].y0) / BHr, (x1 - C[i].x0 + 63) / 64, (y1 - C[i].y0 + BHr - 1) / BHr });
-        }
-    }
-    for (int i = 0; i < L; i++) {
-        // at most kMaxRects (level 0) / kMaxRectsUpper travel with a job: merge the pair whose common bounding box adds the fewest blocks
-        // (extra blocks only cost time: they hold no owned pixel and write no tile)
-        std::vector<R>& v = lv[i];
-        auto area = [](const R& r) { return (long)(r.x1 - r.x0) * (r.y1 - r.y0); };
-        const int cap = i == 0 ? kMaxRects : kMaxRectsUpper;       // what a job of this level can carry (kernels.hpp)
-        while ((int)v.size() > cap) {
-            size_t ba = 0, bb = 1; long best = -1;
-            for (size_t p = 0; p < v.size(); p++)
-                for (size_t q = p + 1; q < v.size(); q++) {
-                    const R u{ std::min(v[p].x0, v[q].x0), std::min(v[p].y0, v[q].y0), std::max(v[p].x1, v[q].x1), std::max(v[p].y1, v[q].y1) };
-                    const long add = area(u) - area(v[p]) - area(v[q]);
-                    if (best < 0 || add < best) { best = add; ba = p; bb = q; }
-                }
-            v[ba] = R{ std::min(v[ba].x0, v[bb].x0), std::min(v[ba].y0, v[bb].y0), std::max(v[ba].x1, v[bb].x1), std::max(v[ba].y1, v[bb].y1) };
-            v.erase(v.begin() + bb);
-        }
-        w.nrect[i] = (int)v.size();
-        for (int k = 0; k < w.nrect[i]; k++) w.rects[i][k] = BlockRect{ (short)v[k].x0, (short)v[k].y0, (short)v[k].x1, (short)v[k].y1 };
-        if (v.empty()) { w.nrect[i] = 1; w.rects[i][0] = BlockRect{ 0, 0, 0, 0 }; }      // nothing needed at this level: an empty rectangle
-    }
-    // level-0 blocks that run (render_stats, bench --shard strong; the numerator of roofline.frac)
-    if (w.need_n[1] > 0 && level0_need_reach(lay_, w.table_args ? tx * ty : 0, w.nrect[0]) > 0) {
-        // the level-0 blocks pick themselves in the kernel (within 94 px of a rendered cell): counted through the level-1 bitmap, whose
-        // blocks are 2 x 2 of them under nearly the same rule (92 px)
-        int n1 = 0;
-        for (int k = 0; k < (w.need_n[1] + 31) / 32; k++) n1 += __builtin_popcount(need_tmp_[1][k]);
-        w.blocks_run0 = std::min(4.0 * n1, (double)((C[0].x1 - C[0].x0 + 63) / 64) * ((C[0].y1 - C[0].y0 + BHr - 1) / BHr));
-    } else {
-        const int nbx = (C[0].x1 - C[0].x0 + 63) / 64, nby = (C[0].y1 - C[0].y0 + BHr - 1) / BHr;
-        block_bits_.assign((size_t)std::max(nbx, 0) * std::max(nby, 0), 0);
-        for (int k = 0; k < w.nrect[0]; k++)
-            for (int gy = w.rects[0][k].y0; gy < w.rects[0][k].y1; gy++)
-                if (w.rects[0][k].x1 > w.rects[0][k].x0) std::memset(block_bits_.data() + (size_t)gy * nbx + w.rects[0][k].x0, 1, (size_t)(w.rects[0][k].x1 - w.rects[0][k].x0));
-        for (uint8_t v : block_bits_) w.blocks_run0 += v;
-    }
-    px_level0_ += w.blocks_run0 * 64 * BHr;
+    // (the level-0 job carries rectangles wherever the plan consults the reach)
+    const bool rects = w.plan.plan(table_tmp_.data(), w.tx, w.ty, w.L, w.pb, w.cells, w.sharded, w.culled_any, opt_.fused, BHr,
+                                   level0_need_reach(lay_, w.table_args ? w.tx * w.ty : 0, 1));
+    const Win& C0 = w.plan.C[0];
+    px_level0_ += rects ? w.plan.blocks_run0 * 64 * BHr : (double)(C0.x1 - C0.x0) * (C0.y1 - C0.y0);
 #if PF_EXPERIMENTS
     static const bool exact_stat = exp_env("PF_CULL_EXACT_STAT") != nullptr;
-    if (exact_stat) cull_exact_stat(w);
+    if (rects && exact_stat) cull_exact_stat(w);
 #endif
-}
-
-// Accounting of a pipelined launch: share of each level's canvas pixels (this rank's tiles) that the blocks which RUN cover: 1 unless the
-// cull or a shard leaves blocks out.  Level 0 with the blocks' own need test (k_levels, need_r0): through the level-1 bitmap here, and --
-// for the launches that are bracketed by events -- exactly, after the launch is out (exact_level0_share).
-void FusionMap::run_shares(const FrameWork& w, double run_share[kMaxLevels], int* exact_r0)
-{
-    const int L = w.L;
-    const Win* C = w.C;
-    *exact_r0 = 0;
-    for (int i = 0; i < kMaxLevels; i++) run_share[i] = 1.0;
-    if (!((w.sharded || w.culled_any) && !w.cells_overflow)) return;
-    const int BHr = level_block_rows(lay_.f32 != 0);
-    for (int i = 0; i < L; i++) {
-        const int nbx = (C[i].x1 - C[i].x0 + 63) / 64, nby = (C[i].y1 - C[i].y0 + BHr - 1) / BHr;
-        if (nbx <= 0 || nby <= 0) continue;
-        double run = 0;
-        const int r0 = i == 0 && w.need_n[1] > 0 ? level0_need_reach(lay_, w.table_args ? w.tx * w.ty : 0, w.nrect[0]) : 0;
-        if (i == 0 && r0 > 0 && prof_would(K_LEVEL0) && cell_rows_.size() == (size_t)4 * w.ty) {
-            *exact_r0 = r0;                             // counted exactly AFTER the launch is out: ~50 us of host time that must not delay it
-            run = w.blocks_run0;
-        } else if (i == 0) run = w.blocks_run0;
-        else if (w.need_n[i] > 0) { for (int k = 0; k < (w.need_n[i] + 31) / 32; k++) run += __builtin_popcount(need_tmp_[i][k]); }
-        else {
-            block_bits_.assign((size_t)nbx * nby, 0);
-            for (int k = 0; k < w.nrect[i]; k++)
-                for (int gy = std::max<int>(w.rects[i][k].y0, 0); gy < std::min<int>(w.rects[i][k].y1, nby); gy++)
-                    for (int gx = std::max<int>(w.rects[i][k].x0, 0); gx < std::min<int>(w.rects[i][k].x1, nbx); gx++) block_bits_[(size_t)gy * nbx + gx] = 1;
-            for (uint8_t v : block_bits_) run += v;
-            if (!w.nrect[i]) run = (double)nbx * nby;
-        }
-        const double ts = kElePixels >> i;
-        run_share[i] = std::min(1.0, run * 64.0 * BHr / std::max(1.0, (double)w.owned_all * ts * ts));
-    }
-}
-
-// the blocks' own need rule (k_levels need_r0) evaluated from the rendered cells' row bitmaps: the share of the level-0 canvas pixels
-// that the blocks which run cover (the column masks once per launch, one AND per block: ~8 us for cfg-A's 7072 blocks)
-double FusionMap::exact_level0_share(const FrameWork& w, int r0)
-{
-    typedef unsigned __int128 u128;
-    const Win* C = w.C;
-    const int BHr = level_block_rows(lay_.f32 != 0);
-    const int nbx = (C[0].x1 - C[0].x0 + 63) / 64, nby = (C[0].y1 - C[0].y0 + BHr - 1) / BHr;
-    static thread_local std::vector<u128> colmask;
-    colmask.assign((size_t)std::max(nbx, 0), 0);
-    for (int gx = 0; gx < nbx; gx++) {
-        const int x0 = std::max(C[0].x0 + gx * 64 - r0, 0) >> 6, x1 = std::min(C[0].x0 + gx * 64 + 63 + r0, w.ccols - 1) >> 6;
-        if (x0 <= x1) colmask[(size_t)gx] = (x1 - x0 >= 127 ? ~(u128)0 : (((u128)1 << (x1 - x0 + 1)) - 1)) << x0;
-    }
-    long run = 0;
-    for (int gy = 0; gy < nby; gy++) {
-        const int y0 = std::max(C[0].y0 + gy * BHr - r0, 0) >> 6, y1 = std::min(C[0].y0 + gy * BHr + BHr - 1 + r0, w.crows - 1) >> 6;
-        u128 rowsum = 0;
-        for (int r = y0; r <= y1; r++) rowsum |= cell_rows_[(size_t)r];
-        if (!rowsum) continue;
-        const uint64_t lo = (uint64_t)rowsum, hi = (uint64_t)(rowsum >> 64);
-        for (int gx = 0; gx < nbx; gx++) run += ((lo & (uint64_t)colmask[(size_t)gx]) | (hi & (uint64_t)(colmask[(size_t)gx] >> 64))) != 0;
-    }
-    const double n0 = (double)w.owned_all * kElePixels * kElePixels;
-    return std::min(1.0, run * 64.0 * BHr / std::max(1.0, n0));
 }
 
 // fused = 1: one launch per keyframe -- this frame's level 0 plus the pending upper levels of the frames before it
@@ -1373,12 +1100,13 @@ bool FusionMap::launch_fused_pipeline(const QueuedFrame& f, FrameWork& w)
     const double E = 3 * es + 4, owned_tiles = w.owned_all;       // algorithmic bytes: every canvas tile of this rank, culled or not
     double run_share[kMaxLevels];
     int exact_r0 = 0;
-    run_shares(w, run_share, &exact_r0);
+    LevelPlan& pl = w.plan;
+    pl.run_shares(w.owned_all, prof_would(K_LEVEL0), run_share, &exact_r0);
     PipeFrame cur;
     cur.valid = true; cur.ring = w.ring; cur.tx = w.tx; cur.crows = w.crows; cur.ccols = w.ccols;
     for (int i = 0; i < L; i++) {
-        cur.C[i] = w.C[i]; cur.nrect[i] = w.nrect[i];
-        for (int k = 0; k < w.nrect[i]; k++) cur.rect[i][k] = w.rects[i][k];
+        cur.C[i] = pl.C[i]; cur.nrect[i] = pl.nrect[i];
+        for (int k = 0; k < pl.nrect[i]; k++) cur.rect[i][k] = pl.rects[i][k];
         const double ts = kElePixels >> i, n = owned_tiles * ts * ts;
         // algorithmic bytes: frame read once + per tile-level pixel 4 (stored weight) + E (payload)
         const double tile_bytes = n * (4 + E) + (i + 1 == L ? n / 4 * (4 + E) : 0), frame_bytes_read = i == 0 ? (double)w.a.src_cn * f.rows * f.cols : 0;
@@ -1386,13 +1114,13 @@ bool FusionMap::launch_fused_pipeline(const QueuedFrame& f, FrameWork& w)
         cur.bytes_run[i] = tile_bytes * run_share[i] + frame_bytes_read;      // the part of the canvas whose blocks run
     }
     if (w.table_args) { cur.table_args = table_tmp_.data(); cur.table_n = w.tx * w.ty; }
-    for (int i = 1; i < L; i++) { cur.need_n[i] = w.need_n[i]; if (w.need_n[i] > 0) std::memcpy(cur.need_bits[i], need_tmp_[i], sizeof(uint32_t) * (size_t)((w.need_n[i] + 31) / 32)); }
+    for (int i = 1; i < L; i++) { cur.need_n[i] = pl.need_n[i]; if (pl.need_n[i] > 0) std::memcpy(cur.need_bits[i], pl.need_bits[i], sizeof(uint32_t) * (size_t)((pl.need_n[i] + 31) / 32)); }
     if (!launch_pipeline(&cur, &w.a, w.src)) return false;
     if (exact_r0 > 0 && prof_on_ && !prof_pending_.empty()) {
         // this launch is bracketed by events: replace the level-0 job's estimated run share in its record by the exact one -- now that
         // the launch is on its way
         const double n0 = owned_tiles * kElePixels * kElePixels, tile_bytes0 = n0 * (4 + E) + (L == 1 ? n0 / 4 * (4 + E) : 0);
-        prof_pending_.back().bytes_run += tile_bytes0 * (exact_level0_share(w, exact_r0) - run_share[0]);
+        prof_pending_.back().bytes_run += tile_bytes0 * (pl.exact_level0_share(w.owned_all, exact_r0) - run_share[0]);
     }
     return true;
 }
@@ -1406,7 +1134,7 @@ bool FusionMap::launch_level_streams(const QueuedFrame& f, FrameWork& w)
     const int L = w.L;
     const size_t es = lay_.f32 ? 4 : 2;
     const double E = 3 * es + 4;
-    const Win* C = w.C;
+    const Win* C = w.plan.C;
     const unsigned long long fidx = frame_seq_ - 1;
     const int slot = (int)(fidx % kLvlRing);
     DevBuf* gw = (fidx & 1) ? gw2_ : gw_;
@@ -1456,7 +1184,7 @@ bool FusionMap::launch_per_op(const QueuedFrame& f, FrameWork& w)
     launch_warp(stream_, lay_.f32, w.src, w.a, g_[0].p, (float*)wgt_[0].p);
     prof_end();
     for (int i = 0; i < L; i++) {
-        const Win& d = w.need[i + 1];
+        const Win& d = w.plan.need[i + 1];
         const double nd = (double)(d.x1 - d.x0) * (d.y1 - d.y0);
         prof_begin(K_PYRDOWN_IMG, nd * 4 * 3 * es + nd * 3 * es);
         launch_pyrdown(stream_, lay_.f32 ? 1 : 0, g_[i].p, w.crows >> i, w.ccols >> i, g_[i + 1].p, d.y0, d.y1, d.x0, d.x1);
@@ -1505,7 +1233,7 @@ bool FusionMap::retire_frame(const QueuedFrame& f, FrameWork& w, bool fused)
 void FusionMap::cull_exact_stat(const FrameWork& w)
 {
     const int L = w.L, tx = w.tx, crows = w.crows, ccols = w.ccols, BHr = level_block_rows(lay_.f32 != 0);
-    const Win* C = w.C;
+    const Win* C = w.plan.C; const LevelPlan& pl = w.plan;
     const int R0 = 94, nbx = (C[0].x1 - C[0].x0 + 63) / 64, nby = (C[0].y1 - C[0].y0 + BHr - 1) / BHr;
     long cnt = 0;
     for (int gy = 0; gy < nby; gy++)
@@ -1525,7 +1253,7 @@ void FusionMap::cull_exact_stat(const FrameWork& w)
         for (int gy = 0; gy < nbyi; gy++)
             for (int gx = 0; gx < nbxi; gx++) {
                 bool inr = false;
-                for (int k = 0; k < w.nrect[i]; k++) inr = inr || (gx >= w.rects[i][k].x0 && gx < w.rects[i][k].x1 && gy >= w.rects[i][k].y0 && gy < w.rects[i][k].y1);
+                for (int k = 0; k < pl.nrect[i]; k++) inr = inr || (gx >= pl.rects[i][k].x0 && gx < pl.rects[i][k].x1 && gy >= pl.rects[i][k].y0 && gy < pl.rects[i][k].y1);
                 up_rect_[i] += inr;
                 const int x0 = ((C[i].x0 + gx * 64) << i) - reach, x1 = ((C[i].x0 + gx * 64 + 64) << i) - 1 + reach;
                 const int y0 = ((C[i].y0 + gy * BHr) << i) - reach, y1 = ((C[i].y0 + gy * BHr + BHr) << i) - 1 + reach;
@@ -1549,122 +1277,6 @@ int FusionMap::render_log(long long* out, int cap)
     const int n = (int)std::min<size_t>(render_log_.size(), (size_t)std::max(cap, 0));
     for (int i = 0; i < n; i++) out[i] = render_log_[render_log_.size() - (size_t)n + (size_t)i];
     return (int)render_log_.size();
-}
-
-// May this frame's tiles be culled?  Only for a tame map: every canvas corner (with the pyramid halo) in front of the camera and
-// far inside the int range, as the kernels' fast path assumes -- anything else renders every tile.
-bool FusionMap::cull_frame_ok(const double M[9], int crows, int ccols) const
-{
-    const double xs[2] = { -600.0, ccols + 600.0 }, ys[2] = { -600.0, crows + 600.0 };
-    int sign = 0;
-    for (int i = 0; i < 4; i++) {
-        const double x = xs[i & 1], y = ys[i >> 1], W = M[6] * x + M[7] * y + M[8];
-        if (!(std::fabs(W) > 1e-12) || !std::isfinite(W)) return false;
-        const int sg = W > 0 ? 1 : -1;
-        if (sign && sg != sign) return false;
-        sign = sg;
-        if (!(std::fabs((M[0] * x + M[1] * y + M[2]) / W) < 1.0e7) || !(std::fabs((M[3] * x + M[4] * y + M[5]) / W) < 1.0e7)) return false;
-    }
-    return true;
-}
-
-// The canvas lattice (64 (k - dil), 64 (m - dil)), k = 0 .. ccols / 64 + 2 dil, mapped into the source frame: position, squared distance
-// from the image centre, inside-the-frame flag.  A cell's dilated rectangle has its corners on it.  Points are mapped on first use
-// (a shard asks for an eighth of them); one division per point, no square root.
-void FusionMap::cull_lattice(const double M[9], int crows, int ccols, int cols, int rows, int dil, bool map_all)
-{
-    lat_.all = map_all;
-    lat_.dil = dil;                                             // dilation of a cell in lattice steps of 64 pixels
-    lat_.nx = ccols / 64 + 2 * dil + 1; lat_.ny = crows / 64 + 2 * dil + 1;
-    const size_t n = (size_t)lat_.nx * lat_.ny;
-    lat_.sx.resize(n); lat_.sy.resize(n); lat_.d.resize(n); lat_.in.assign(n, 2);          // 2: not mapped yet
-    lat_.xc = (double)(cols / 2); lat_.yc = (double)(rows / 2); lat_.dis_max = std::sqrt(lat_.xc * lat_.xc + lat_.yc * lat_.yc);
-    lat_.inv_dis_max = 1.0 / lat_.dis_max;
-    lat_.cols = cols; lat_.rows = rows;
-    for (int i = 0; i < 9; i++) lat_.M[i] = M[i];
-    if (!map_all) return;                                       // a shard that owns a small part of the canvas asks for a fraction of the points: on first use
-    // unsharded (or a shard that owns most of this canvas: the replicas of bench.py's weak mode own all of it), every point is needed (a cell's
-    // dilated rectangle has its corners on neighbouring points): all of them now, row by row,
-    // in loops without branches that the compiler turns into packed divisions (a third of the time of mapping them one by one)
-    const double xc = lat_.xc, yc = lat_.yc, cmax = cols - 2.0, rmax = rows - 2.0;
-    for (int m = 0; m < lat_.ny; m++) {
-        const double y = 64.0 * (m - dil), n0 = M[1] * y + M[2], n1 = M[4] * y + M[5], w0 = M[7] * y + M[8];
-        double* __restrict__ sx = lat_.sx.data() + (size_t)m * lat_.nx; double* __restrict__ sy = lat_.sy.data() + (size_t)m * lat_.nx;
-        double* __restrict__ d = lat_.d.data() + (size_t)m * lat_.nx; unsigned char* __restrict__ in = lat_.in.data() + (size_t)m * lat_.nx;
-        for (int k = 0; k < lat_.nx; k++) {
-            const double x = 64.0 * (k - dil), iw = 1.0 / (M[6] * x + w0);
-            const double px = (M[0] * x + n0) * iw, py = (M[3] * x + n1) * iw, dx = px - xc, dy = py - yc;
-            sx[k] = px; sy[k] = py; d[k] = dx * dx + dy * dy;
-        }
-        for (int k = 0; k < lat_.nx; k++) in[k] = (unsigned char)((sx[k] >= 1.0) & (sx[k] <= cmax) & (sy[k] >= 1.0) & (sy[k] <= rmax));
-    }
-}
-
-inline size_t FusionMap::lattice_point(int k, int m)
-{
-    const size_t o = (size_t)m * lat_.nx + k;
-    if (lat_.in[o] == 2) {
-        const double* M = lat_.M;
-        const double x = 64.0 * (k - lat_.dil), y = 64.0 * (m - lat_.dil), iw = 1.0 / (M[6] * x + M[7] * y + M[8]);
-        const double px = (M[0] * x + M[1] * y + M[2]) * iw, py = (M[3] * x + M[4] * y + M[5]) * iw;
-        lat_.sx[o] = px; lat_.sy[o] = py;
-        const double dx = px - lat_.xc, dy = py - lat_.yc;
-        lat_.d[o] = dx * dx + dy * dy;
-        lat_.in[o] = px >= 1.0 && px <= lat_.cols - 2.0 && py >= 1.0 && py <= lat_.rows - 2.0;
-    }
-    return o;
-}
-
-// The radial weight (weightImage, .cpp:396-418, gathered at the NEAREST source pixel, 0 outside the frame) over the canvas rectangle with
-// lattice corners (k, m) .. (k + span + 2 dil, m + span + 2 dil) -- a cell of a tile (span lattice steps on a side) dilated by 64 dil
-// pixels -- against `wlb`, the lower bound of what the cell stores:
-//   returns true when every weight the keyframe can have there is below wlb (the cell is out);
-//   *wmin <= every weight it has there (0 unless the rectangle maps wholly inside the frame).
-// The rectangle maps to a convex quadrilateral Q of the source plane (M is projective and W keeps its sign, cull_frame_ok); the weight
-// falls with the distance from the image centre c, so the largest weight sits at the point of Q nearest to c and the smallest at its
-// farthest corner.  "Largest weight < wlb" <=> dist(c, Q) > T, T the distance at which the weight -- with the margins below -- reaches
-// wlb; decided from the corners alone when one of them lies within T (most cells that stay in), by the exact point-to-quadrilateral
-// distance otherwise.  Margins: 2 source pixels for the nearest-pixel rounding (0.71) and the float arithmetic of the kernels, 1e-5 on
-// the weight for the pyramid's own rounding.
-bool FusionMap::cell_out(int k, int m, int span, int weight_type, float wlb, bool want_out, float* wmin)
-{
-    const int e = span + 2 * lat_.dil;                          // lattice steps across the dilated cell
-    const size_t c[4] = { lattice_point(k, m), lattice_point(k + e, m), lattice_point(k + e, m + e), lattice_point(k, m + e) };
-    const double d2[4] = { lat_.d[c[0]], lat_.d[c[1]], lat_.d[c[2]], lat_.d[c[3]] };
-    const double mpx = cull_margin_px_, mw = cull_margin_w_;       // 2 source pixels, 1e-5 (see the header)
-    if (wmin) {                                                    // (nullptr: only the question whether the cell is out)
-        *wmin = 0.f;
-        // (weight type 0: wmin can exceed wlb only if the farthest corner lies within (1 - 1e-5 - wlb) dis_max - 2 of the centre -- in the steady
-        // state it rarely does, and the square root is not taken)
-        const double far2 = std::max(std::max(d2[0], d2[1]), std::max(d2[2], d2[3]));
-        const double tw = weight_type == 0 ? (1.0 - mw - (double)wlb) * lat_.dis_max - mpx : 1e300;
-        if ((lat_.in[c[0]] & lat_.in[c[1]] & lat_.in[c[2]] & lat_.in[c[3]]) == 1 && tw > 0 && far2 < tw * tw * (1.0 + 1e-9)) {
-            const double dfar = std::sqrt(far2) + mpx;
-            double w = 1.0 - dfar * lat_.inv_dis_max;
-            if (weight_type != 0) w = w > 0 ? w * w : 0.0;
-            w -= mw;
-            if (w > 2e-5) *wmin = (float)w;
-        }
-    }
-    if (!want_out || !(wlb > 2e-5f)) return false;                // nothing known about the stored weights (or a fresh tile): in
-    // T: weight(T - mpx) + mw == wlb
-    double g = (double)wlb - mw;
-    if (weight_type != 0) g = std::sqrt(g);
-    const double T = mpx + lat_.dis_max * (1.0 - g), T2 = T * T;
-    if (d2[0] <= T2 || d2[1] <= T2 || d2[2] <= T2 || d2[3] <= T2) return false;      // a corner within T
-    bool pos = true, neg = true; double dnear2 = 1e300;
-    for (int i = 0; i < 4; i++) {
-        const size_t a = c[i], b = c[(i + 1) & 3];
-        const double ex = lat_.sx[b] - lat_.sx[a], ey = lat_.sy[b] - lat_.sy[a], px = lat_.xc - lat_.sx[a], py = lat_.yc - lat_.sy[a];
-        const double cr = ex * py - ey * px;
-        pos = pos && cr >= 0; neg = neg && cr <= 0;
-        const double e2 = ex * ex + ey * ey, dot = px * ex + py * ey;
-        // squared distance from c to the segment: the end points are the corners (known to lie beyond T), the foot of the perpendicular counts
-        // only when it falls inside the segment
-        if (dot > 0 && dot < e2) dnear2 = std::min(dnear2, cr * cr / e2);
-    }
-    if (pos || neg) return false;                               // the centre lies inside Q: the keyframe's best weights are here
-    return dnear2 > T2;
 }
 
 // Retirement without an event per frame (see the header): count the submission, drop a marker now and then.

@@ -5,6 +5,7 @@
 #include "geometry.hpp"
 #include "kernels.hpp"
 #include "dist_plan.hpp"
+#include "frame_plan.hpp"
 #include "env.hpp"
 #include "image_io.hpp"
 #include "jpeg_encode.hpp"
@@ -157,12 +158,7 @@ public:
     // draw()'s Fuse2Google gate and operands for tile (ix, iy) (MultiBandMap2DCPU.cpp:709-712, :730-735, :744): false when the tile
     // has no pyramid, or lies on the rim of the dense grid while HighQualityShow is on
     bool map_update_inputs(int ix, int iy, double plane7[7], double mn[2], double* ele, int* x, int* y);
-    // the cull of render_frame (tiles in which a keyframe cannot win the select): see there
-    bool cull_frame_ok(const double M[9], int crows, int ccols) const;
-    // source positions of the canvas lattice points (-64 + 64 k, -64 + 64 m) the cells' dilated rectangles have their corners on
-    void cull_lattice(const double M[9], int crows, int ccols, int cols, int rows, int dil, bool map_all);
-    size_t lattice_point(int k, int m);
-    bool cell_out(int k, int m, int span, int weight_type, float wlb, bool want_out, float* wmin);
+    // the cull of render_frame (tiles in which a keyframe cannot win the select): see there, and frame_plan.hpp
     long long culled_tiles() { std::lock_guard<std::mutex> l(mu_); (void)drain(); return n_culled_tiles_; }
     void set_cull(bool on) { std::lock_guard<std::mutex> l(mu_); (void)drain(); cull_on_ = on; }       // default: on unless PF_CULL=0
     long long culled_cells() { std::lock_guard<std::mutex> l(mu_); (void)drain(); return n_culled_cells_; }
@@ -209,6 +205,10 @@ public:
 private:
     bool render_frame(const QueuedFrame& f);                       // .cpp:311-558
     bool spread_map(double xmin, double ymin, double xmax, double ymax);   // .cpp:561-604
+    // footprint -> bounding box -> spreadMap when it leaves the grid -> tile range r (dense index); box: xmin, ymin, xmax, ymax
+    bool canvas_range(const double pts[8], Win& r);
+    void tile_range(double xmin, double ymin, double xmax, double ymax, Win& r) const;
+    bool frame_mismatch(int type, int cols, int rows) const { return (type != PF_8UC3 && type != PF_8UC4) || cols != cam_.w || rows != cam_.h; }
     void worker();                                                 // .cpp:619-635
     int  acquire_slot(size_t bytes);
     bool upload(const pf_image* img, int slot);
@@ -239,15 +239,10 @@ private:
     bool cull_on_ = !(std::getenv("PF_CULL") && std::atoi(std::getenv("PF_CULL")) == 0);
     long long n_culled_tiles_ = 0;              // tiles left out of launches by the cull (diagnostics)
     long long n_culled_cells_ = 0;              // 64 x 64 cells of rendered tiles switched off by it
-    // Margins of the cull's bounds (cell_out): source pixels added to / taken from a distance before it becomes a weight (the nearest-pixel
-    // rounding of the weight gather, 0.71 px, and the float arithmetic of the kernels), and what is taken from / added to a weight (the
-    // pyramid's own rounding).  PF_CULL_MARGIN_PX / PF_CULL_MARGIN_W (experiments library) override them for the sensitivity runs of tools/cull_soak.py
-    // (profiles/r05_cull_margins.md: mismatches against the oracle per setting -- the safety factor, measured); defaults 2 px, 1e-5.
-    double cull_margin_px_ = exp_env_double("PF_CULL_MARGIN_PX", 2.0);
-    double cull_margin_w_ = exp_env_double("PF_CULL_MARGIN_W", 1e-5);
-    int cull_sub_ = exp_env_int("PF_CULL_SUB", 4) == 2 ? 2 : 4;      // cells per tile edge (experiments library: 2 = quadrants)
-    struct Lattice { bool all = false; int nx = 0, ny = 0, dil = 1, cols = 0, rows = 0; double xc = 0, yc = 0, dis_max = 1, inv_dis_max = 1, M[9] = {}; std::vector<double> sx, sy, d; std::vector<unsigned char> in; };
-    Lattice lat_;                                   // of the keyframe being admitted / rendered
+    // Margins of the cull's bounds (frame_plan.hpp, CullMargins).  PF_CULL_MARGIN_PX / PF_CULL_MARGIN_W (experiments library) override them for
+    // the sensitivity runs of tools/cull_soak.py (profiles/r05_cull_margins.md: mismatches against the oracle per setting -- the safety
+    // factor, measured); defaults 2 px, 1e-5.  PF_CULL_SUB (experiments library): cells per tile edge, 2 = quadrants
+    CullMargins cull_margins_{ exp_env_double("PF_CULL_MARGIN_PX", 2.0), exp_env_double("PF_CULL_MARGIN_W", 1e-5), exp_env_int("PF_CULL_SUB", 4) == 2 ? 2 : 4 };
     Camera cam_{};
     double ele_size_ = 0, ele_size_inv_ = 0, length_pixel_ = 0, length_pixel_inv_ = 0;
     double min_[3]{}, max_[3]{};
@@ -270,7 +265,6 @@ private:
     bool       table_in_args_ = true;               // PF_TABLE_COPY=1 forces the copy path (A/B, tests)
     DevBuf     table_dev_[kTableRing];
     std::vector<uint64_t> table_tmp_;               // a frame's entries while they are being built
-    std::vector<uint8_t>  block_bits_;              // level-0 blocks a shard runs (render_stats only)
     size_t     table_cap_ = 0;
     hipEvent_t table_ev_[kTableRing]{};             // fused = 2/3: last reader of the ring slot done (own stream)
     bool       table_pending_[kTableRing]{};
@@ -289,7 +283,6 @@ private:
     unsigned long long frame_seq_ = 0;
 
     // pipelined level launches (opt_.fused == 1): pipe_[s] is the frame whose level s runs in the next launch
-    struct Win { int x0, x1, y0, y1; };
     struct PipeFrame { bool valid = false; int ring = 0, tx = 0, crows = 0, ccols = 0; Win C[kMaxLevels]; double bytes[kMaxLevels], bytes_run[kMaxLevels];
                        int nrect[kMaxLevels]; BlockRect rect[kMaxLevels][kMaxRects];        // LevelLaunch::rect of each level
                        uint32_t need_bits[kMaxLevels][kNeedWords]; int need_n[kMaxLevels] = {};    // LevelLaunch::need_bits of the upper levels (need_n 0: none)
@@ -302,28 +295,24 @@ private:
         double pts[8]; int xminInt, yminInt, xmaxInt, ymaxInt;
         int tx, ty, L, crows, ccols; double M0[9], Minv[9];
         const uint8_t* src;
-        // build_tile_table(): the cull, the owned tiles and their boxes (tiles; level-0 pixels), the hash cells of the need rectangles
-        bool sharded, cull, culled_any, cells_overflow;
+        // build_tile_table(): the cull (lat: the keyframe's lattice), the owned tiles and their boxes (tiles; level-0 pixels), the hash cells of the need rectangles
+        bool sharded, cull, culled_any; Lattice* lat;
         bool pre_raised;                                          // the keyframe's bounds entered wlb when it was admitted (lookahead): not worked out again
         Tile* const* tiles_known;                                 // ... and its canvas' tiles are known from then (nullptr: look them up)
         struct Raise { Tile* t; int q; float w; };                // (cell, wmin of this keyframe): applied once the frame is in
         std::vector<Raise> raise; std::vector<Tile*> culled, touched;
-        struct Cell { int cx, cy, x0, y0, x1, y1; };              // hash cell; box of what is rendered in it, level-0 pixels
-        Cell cells[64]; int ncells;
+        CellList cells;
         int bx0, bx1, by0, by1, owned, owned_all;
-        int pbx0, pbx1, pby0, pby1;
-        // level_windows() / plan_fused_levels()
-        Win need[kMaxLevels], C[kMaxLevels];
-        BlockRect rects[kMaxLevels][kMaxRects]; int nrect[kMaxLevels]; int need_n[kMaxLevels];
-        double blocks_run0;
+        Win pb;
+        // where each level is needed and which blocks run (frame_plan.hpp)
+        LevelPlan plan;
         // place_table() / warp_args()
         int ring; bool table_args; const uint64_t* dtab;
         WarpArgs a;
         void reset() {
             raise.clear(); culled.clear(); touched.clear();
-            culled_any = cells_overflow = false; ncells = 0; owned = owned_all = 0; blocks_run0 = 0;
-            for (int i = 0; i < kMaxLevels; i++) { nrect[i] = 0; need_n[i] = 0; }
-            src = nullptr; ring = 0; table_args = false; dtab = nullptr; sharded = cull = pre_raised = false; tiles_known = nullptr;
+            culled_any = cells.overflow = false; cells.n = 0; owned = owned_all = 0; plan.reset();
+            src = nullptr; ring = 0; table_args = false; dtab = nullptr; sharded = cull = pre_raised = false; tiles_known = nullptr; lat = nullptr;
         }
     };
     FrameWork fw_;
@@ -349,7 +338,6 @@ private:
     unsigned since_drain_ = 0;
     std::vector<Lattice> lat_pool_;                 // buffers of rendered keyframes' lattices, reused
     std::vector<std::vector<Tile*>> tiles_pool_;
-    std::vector<double> pair_d_; std::vector<unsigned char> pair_in_;      // pre_raise scratch
     bool lookahead_ok() const { return opt_.lookahead > 0 && (single_band_ || (opt_.fused == 1 && band_num_ >= 1)) && cull_on_; }     // wherever the cull runs
     bool render_front();                            // renders pending_.front() and removes it
     bool drain();                                   // ... all of them; mu_ held.  First thing every reader of tiles, flags or counters does
@@ -357,21 +345,16 @@ private:
     void pre_raise(FrameWork& w, std::vector<Tile*>& tiles);
     int  frame_canvas(const QueuedFrame& f, FrameWork& w);
     bool build_tile_table(const QueuedFrame& f, FrameWork& w);
-    void level_windows(FrameWork& w);
     bool reserve_frame_workspace(FrameWork& w);
     bool place_table(FrameWork& w);
     void warp_args(const QueuedFrame& f, FrameWork& w);
     void plan_fused_levels(FrameWork& w);
-    void run_shares(const FrameWork& w, double run_share[kMaxLevels], int* exact_r0);
-    double exact_level0_share(const FrameWork& w, int r0);
     bool launch_single_band(const QueuedFrame& f, FrameWork& w);
     bool launch_fused_pipeline(const QueuedFrame& f, FrameWork& w);
     bool launch_level_streams(const QueuedFrame& f, FrameWork& w);
     bool launch_per_op(const QueuedFrame& f, FrameWork& w);
     bool retire_frame(const QueuedFrame& f, FrameWork& w, bool fused);
     void log_rendered(const QueuedFrame& f);
-    uint32_t need_tmp_[kMaxLevels][kNeedWords];     // render_frame scratch: the upper levels' need bitmaps of the keyframe being fed
-    std::vector<unsigned __int128> cell_rows_;      // render_frame scratch: rendered cells of the canvas, one 128-bit row per cell row
     unsigned long long launch_seq_ = 0;             // parity selects the GW buffer set a launch writes
     bool flushing_ = false;
     bool launch_pipeline(const PipeFrame* cur, const WarpArgs* wa, const uint8_t* src);

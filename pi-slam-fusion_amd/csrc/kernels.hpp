@@ -10,14 +10,12 @@
 //                packed (256>>i)^2 image; offsets in TileLayout.
 //   tile table : per frame, tilesX*tilesY uint64 = slot base address | fresh bit.
 #pragma once
+#include "plan_limits.hpp"      // kElePixels, kMaxLevels, kArgTable, kMaxRects, kMaxRectsUpper, kNeedWords, BlockRect
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstddef>
 
 namespace pf {
-
-constexpr int kElePixels = 256;
-constexpr int kMaxLevels = 9;
 
 struct TileLayout {
     int      nlev;          // bandNum + 1
@@ -87,11 +85,6 @@ void launch_level(hipStream_t s, const TileLayout& lay, int level, int rows, int
 
 // Pipelined form of the same kernel: ONE launch carries several independent level jobs (level 0 of the
 // newest frame, level 1 of the frame before it, ...), each with its own tile table and GW buffers.
-constexpr int kArgTable = 256;      // tile-table entries that can travel inside the kernel arguments of a launch
-constexpr int kMaxRects = 8;        // need rectangles of a level-0 job (tile-sharded canvases, the cull): what LevelLaunch can hold
-constexpr int kMaxRectsUpper = 4;   // ... of an upper-level job (their need bitmaps took the room in the kernel arguments; they are the fallback there)
-constexpr int kNeedWords = 100;     // 32-bit words of need bitmaps a launch can carry for its upper-level jobs (kernel arguments are 4 KB)
-struct BlockRect { short x0, y0, x1, y1; };      // [x0,x1) x [y0,y1) in blocks of the job's block grid
 struct LevelLaunch {
     int level, rows, cols;          // pyramid level and its canvas extent
     int cx0, cy0, cx1, cy1;         // compute region

@@ -1,0 +1,382 @@
+// frame_plan_check.cpp -- the keyframe plan (pi-slam-fusion_amd/csrc/frame_plan.hpp, the very code the library compiles) against models
+// written from its rules: plain loops over cells, blocks and pixels, no bit tricks, nothing shared with the header but its types.
+//   (a) need bitmaps  (b) exact_level0_blocks  (c) need windows and compute regions  (d) need rectangles
+//   (e) cell_out / cull_frame_ok  (f) raise_bounds, both routes  (g) tile_cull
+// Built with -fsanitize=address,undefined (tests/cpp/Makefile, target plan); prints one line of counts, tests/test_frame_plan.py asserts that
+// every branch was exercised.  Exit status 1 and a line "VIOLATION ..." on the first mismatch.
+#include "frame_plan.hpp"
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+
+using namespace pf;
+
+static void fail(const std::string& what) { std::printf("VIOLATION %s\n", what.c_str()); std::exit(1); }
+#define CHECK(c, ...) do { if (!(c)) { char b_[400]; std::snprintf(b_, sizeof b_, __VA_ARGS__); fail(std::string(#c) + ": " + b_); } } while (0)
+
+static uint64_t g_rng = 20261018;
+static unsigned rnd() { g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(g_rng >> 33); }
+
+static long n_bits_set, n_bits_clear, n_bitmaps, n_no_bitmap_wide, n_no_bitmap_big, n_overflow, n_exact, n_exact_blocks, n_windows, n_regions,
+            n_rect_plans, n_merge0, n_mergeU, n_must, n_empty_rect, n_union, n_run_bitmap;
+
+static const int BH = 32;
+
+// ------------------------------------------------------------------------------------------------ (a) - (d): one canvas, one set of out-masks
+struct Canvas { int tx, ty, L, Bc; std::vector<int> present; std::vector<unsigned> out; };      // out: bit 4 * row + column = the cell is NOT rendered
+
+static bool rendered(const Canvas& c, int cx, int cy)       // cell (cx, cy) of the canvas, in cells of 64 x 64 pixels
+{
+    const int t = (cy / 4) * c.tx + cx / 4;
+    return c.present[t] && !((c.out[t] >> (4 * (cy % 4) + cx % 4)) & 1);
+}
+
+// one axis of the model of (c): which pixels of Gaussian level i are needed when [b0, b1) (level-0 pixels) is rendered, canvas extent n0
+static void mark_axis(int b0, int b1, int n0, int L, std::vector<char> G[kMaxLevels], std::vector<char> lap[kMaxLevels])
+{
+    for (int i = 0; i <= L; i++) {
+        const int n = n0 >> i;
+        G[i].assign(n, 0); lap[i].assign(n, 0);
+        for (int p = 0; p < n; p++) lap[i][p] = ((long)p << i) < b1 && (((long)p + 1) << i) > b0;     // the pixel's level-0 footprint meets the box
+    }
+    for (int i = 0; i <= L; i++)
+        for (int p = 0; p < (n0 >> i); p++) {
+            if (!lap[i][p]) continue;
+            G[i][p] = 1;                                                        // a Laplacian pixel needs G_i(p) ...
+            if (i < L) for (int q = (p >> 1) - 1; q <= (p >> 1) + 1; q++) if (q >= 0 && q < (n0 >> (i + 1))) G[i + 1][q] = 1;      // ... and G_{i+1} at (p >> 1) +- 1
+        }
+    for (int i = L - 1; i >= 0; i--)
+        for (int p = 0; p < (n0 >> (i + 1)); p++) {
+            if (!G[i + 1][p]) continue;
+            for (int q = 2 * p - 2; q <= 2 * p + 2; q++) if (q >= 0 && q < (n0 >> i)) G[i][q] = 1;      // G_{i+1}(p) needs G_i at 2p-2 .. 2p+2
+        }
+}
+
+static void bbox(const std::vector<char>& v, int& lo, int& hi) { lo = (int)v.size(); hi = 0; for (int p = 0; p < (int)v.size(); p++) if (v[p]) { lo = std::min(lo, p); hi = std::max(hi, p + 1); } }
+
+static LevelPlan g_plan, g_plan2;       // kept between canvases, as the library keeps its own
+
+static void check_canvas(const Canvas& c)
+{
+    const int tx = c.tx, ty = c.ty, L = c.L, crows = ty * 256, ccols = tx * 256;
+    // what build_tile_table hands over: entries, the box around the rendered cells, the hash cells with the rendered cells row by row as runs
+    std::vector<uint64_t> table((size_t)tx * ty, 0);
+    Win pb{ 1 << 30, 0, 1 << 30, 0 };
+    CellList cells;
+    bool culled_any = false;
+    int n_rendered = 0;
+    for (int y = 0; y < ty; y++)
+        for (int x = 0; x < tx; x++) {
+            const int t = y * tx + x;
+            if (!c.present[t]) { culled_any = true; continue; }
+            table[t] = 0x1000ull | ((uint64_t)c.out[t] << 48);
+            if (c.out[t]) culled_any = true;
+            for (int r = 0; r < 4; r++) {
+                int c0 = 4, c1 = -1;
+                for (int q = 0; q < 4; q++) if (!((c.out[t] >> (4 * r + q)) & 1)) { c0 = std::min(c0, q); c1 = std::max(c1, q); n_rendered++; }
+                if (c1 < 0) continue;
+                const int x0 = 256 * x + 64 * c0, x1 = 256 * x + 64 * (c1 + 1), y0 = 256 * y + 64 * r, y1 = y0 + 64;
+                pb.x0 = std::min(pb.x0, x0); pb.x1 = std::max(pb.x1, x1); pb.y0 = std::min(pb.y0, y0); pb.y1 = std::max(pb.y1, y1);
+                cells.add(x / c.Bc, y / c.Bc, x0, y0, x1, y1);
+            }
+        }
+    if (!n_rendered) return;
+    if (cells.overflow) n_overflow++;
+    const int reach0 = (3 << L) - 2;
+    LevelPlan& P = g_plan;
+    P.reset();
+    P.windows(pb, L, crows, ccols);
+    const bool rects = P.plan(table.data(), tx, ty, L, pb, cells, false, culled_any, 1, BH, reach0 <= 96 && tx * ty <= kArgTable ? reach0 : 0);
+    CHECK(rects == (culled_any && !cells.overflow), "tx %d ty %d L %d", tx, ty, L);
+
+    // (c) windows and compute regions
+    std::vector<char> GX[kMaxLevels], GY[kMaxLevels], LX[kMaxLevels], LY[kMaxLevels];
+    mark_axis(pb.x0, pb.x1, ccols, L, GX, LX); mark_axis(pb.y0, pb.y1, crows, L, GY, LY);
+    for (int i = 0; i <= L; i++) {
+        int x0, x1, y0, y1;
+        bbox(GX[i], x0, x1); bbox(GY[i], y0, y1);
+        for (int p = 0; p < (ccols >> i); p++) CHECK(!GX[i][p] || (p >= P.need[i].x0 && p < P.need[i].x1), "need x level %d pixel %d", i, p);
+        for (int p = 0; p < (crows >> i); p++) CHECK(!GY[i][p] || (p >= P.need[i].y0 && p < P.need[i].y1), "need y level %d pixel %d", i, p);
+        if (i == 0) { x0 = x0 / 64 * 64; x1 = std::min(ccols, (x1 + 63) / 64 * 64); y0 = y0 / 4 * 4; y1 = std::min(crows, (y1 + 3) / 4 * 4); }
+        CHECK(P.need[i].x0 == x0 && P.need[i].x1 == x1 && P.need[i].y0 == y0 && P.need[i].y1 == y1, "need[%d] = %d %d %d %d, model %d %d %d %d (tx %d ty %d L %d)",
+              i, P.need[i].x0, P.need[i].x1, P.need[i].y0, P.need[i].y1, x0, x1, y0, y1, tx, ty, L);
+        n_windows++;
+    }
+    for (int i = 0; i < L; i++) {
+        CHECK(P.C[i].x0 % 2 == 0 && P.C[i].y0 % 2 == 0, "C[%d] origin", i);
+        CHECK(P.C[i].x0 >= 0 && P.C[i].y0 >= 0 && P.C[i].x1 <= (ccols >> i) && P.C[i].y1 <= (crows >> i), "C[%d] inside the canvas", i);
+        for (int p = 0; p < (ccols >> i); p++) CHECK(!LX[i][p] || (p >= P.C[i].x0 && p < P.C[i].x1), "C[%d] holds the rendered box, x %d", i, p);
+        for (int p = 0; p < (crows >> i); p++) CHECK(!LY[i][p] || (p >= P.C[i].y0 && p < P.C[i].y1), "C[%d] holds the rendered box, y %d", i, p);
+        if (i + 1 < L) {
+            CHECK(P.C[i].x0 <= std::max(2 * (P.C[i + 1].x0 - 4), 0) && P.C[i].x1 >= std::min(2 * (P.C[i + 1].x1 + 3), ccols >> i), "C[%d] x against C[%d]", i, i + 1);
+            CHECK(P.C[i].y0 <= std::max(2 * (P.C[i + 1].y0 - 4), 0) && P.C[i].y1 >= std::min(2 * (P.C[i + 1].y1 + 3), crows >> i), "C[%d] y against C[%d]", i, i + 1);
+            n_regions++;
+        }
+    }
+
+    // (a) need bitmaps of the upper levels: every block against every rendered cell
+    std::vector<int> model_bits1;
+    for (int i = 1; i < L; i++) {
+        const int nbx = (P.C[i].x1 - P.C[i].x0 + 63) / 64, nby = (P.C[i].y1 - P.C[i].y0 + BH - 1) / BH;
+        const bool expect = rects && 4 * tx <= 128 && nbx > 0 && nby > 0 && nbx * nby <= 32 * kNeedWords;
+        if (rects && 4 * tx > 128) n_no_bitmap_wide++;
+        if (rects && 4 * tx <= 128 && nbx * nby > 32 * kNeedWords) n_no_bitmap_big++;
+        CHECK(P.need_n[i] == (expect ? nbx * nby : 0), "need_n[%d] = %d (tx %d ty %d L %d)", i, P.need_n[i], tx, ty, L);
+        if (!expect) continue;
+        n_bitmaps++;
+        const long reach = (long)((3 << (L - i)) - 2) << i;
+        for (int gy = 0; gy < nby; gy++)
+            for (int gx = 0; gx < nbx; gx++) {
+                const long bx0 = ((long)(P.C[i].x0 + gx * 64) << i) - reach, bx1 = ((long)(P.C[i].x0 + gx * 64 + 64) << i) - 1 + reach;      // inclusive, level-0 pixels
+                const long by0 = ((long)(P.C[i].y0 + gy * BH) << i) - reach, by1 = ((long)(P.C[i].y0 + gy * BH + BH) << i) - 1 + reach;
+                bool need = false;
+                for (int cy = 0; cy < 4 * ty; cy++)
+                    for (int cx = 0; cx < 4 * tx; cx++)
+                        if (rendered(c, cx, cy) && 64L * cx <= bx1 && 64L * cx + 63 >= bx0 && 64L * cy <= by1 && 64L * cy + 63 >= by0) need = true;
+                const int b = gy * nbx + gx;
+                const bool bit = (P.need_bits[i][b / 32] >> (b % 32)) & 1;
+                CHECK(bit == need, "need bit level %d block (%d, %d): %d, model %d (tx %d ty %d L %d)", i, gx, gy, (int)bit, (int)need, tx, ty, L);
+                (need ? n_bits_set : n_bits_clear)++;
+                if (i == 1) model_bits1.push_back(need);
+            }
+    }
+
+    // (b) the level-0 blocks within the reach of a rendered cell, by the loop of the library's own statistics (cull_exact_stat)
+    if (rects && 4 * tx <= 128 && L >= 2) {
+        const int R0 = reach0, nbx = (P.C[0].x1 - P.C[0].x0 + 63) / 64, nby = (P.C[0].y1 - P.C[0].y0 + BH - 1) / BH;
+        long cnt = 0;
+        for (int gy = 0; gy < nby; gy++)
+            for (int gx = 0; gx < nbx; gx++) {
+                const int x0 = P.C[0].x0 + gx * 64 - R0, x1 = P.C[0].x0 + gx * 64 + 63 + R0, y0 = P.C[0].y0 + gy * BH - R0, y1 = P.C[0].y0 + gy * BH + BH - 1 + R0;
+                bool need = false;
+                for (int qy = std::max(y0, 0) / 64; qy <= std::min(y1, crows - 1) / 64; qy++)
+                    for (int qx = std::max(x0, 0) / 64; qx <= std::min(x1, ccols - 1) / 64; qx++) need = need || rendered(c, qx, qy);
+                cnt += need;
+            }
+        const long got = P.exact_level0_blocks(R0);
+        CHECK(got == cnt, "exact_level0_blocks %ld, model %ld (tx %d ty %d L %d)", got, cnt, tx, ty, L);
+        n_exact++; n_exact_blocks += cnt;
+    }
+
+    // (d) rectangles
+    if (!rects) return;
+    n_rect_plans++;
+    if (cells.n > kMaxRects) n_merge0++;
+    if (cells.n > kMaxRectsUpper && L >= 2) n_mergeU++;
+    std::vector<char> must[kMaxLevels];
+    int nbx[kMaxLevels], nby[kMaxLevels];
+    for (int i = 0; i < L; i++) {
+        nbx[i] = (P.C[i].x1 - P.C[i].x0 + 63) / 64; nby[i] = (P.C[i].y1 - P.C[i].y0 + BH - 1) / BH;
+        must[i].assign((size_t)nbx[i] * nby[i], 0);
+    }
+    for (int k = 0; k < cells.n; k++) {
+        const CellList::Cell& ce = cells.c[k];
+        std::vector<char> NX[kMaxLevels], NY[kMaxLevels], BX[kMaxLevels], BY[kMaxLevels];
+        mark_axis(ce.x0, ce.x1, ccols, L, NX, BX); mark_axis(ce.y0, ce.y1, crows, L, NY, BY);
+        for (int i = 0; i < L; i++) {
+            // per block column / row: does it hold a pixel of the cell's box; does its part of level i+1 hold a pixel of N[i+1]
+            std::vector<char> xb(nbx[i], 0), xn(nbx[i], 0), yb(nby[i], 0), yn(nby[i], 0);
+            for (int g = 0; g < nbx[i]; g++)
+                for (int p = P.C[i].x0 + g * 64; p < std::min(P.C[i].x0 + g * 64 + 64, P.C[i].x1); p++) { if (BX[i][p]) xb[g] = 1; if (NX[i + 1][p / 2]) xn[g] = 1; }
+            for (int g = 0; g < nby[i]; g++)
+                for (int p = P.C[i].y0 + g * BH; p < std::min(P.C[i].y0 + g * BH + BH, P.C[i].y1); p++) { if (BY[i][p]) yb[g] = 1; if (NY[i + 1][p / 2]) yn[g] = 1; }
+            for (int gy = 0; gy < nby[i]; gy++)
+                for (int gx = 0; gx < nbx[i]; gx++) if ((xb[gx] && yb[gy]) || (xn[gx] && yn[gy])) must[i][(size_t)gy * nbx[i] + gx] = 1;
+        }
+    }
+    for (int i = 0; i < L; i++) {
+        CHECK(P.nrect[i] >= 1 && P.nrect[i] <= (i == 0 ? kMaxRects : kMaxRectsUpper), "nrect[%d] = %d", i, P.nrect[i]);
+        for (int k = 0; k < P.nrect[i]; k++) {
+            const BlockRect& r = P.rects[i][k];
+            CHECK(r.x0 >= 0 && r.y0 >= 0 && r.x0 <= r.x1 && r.y0 <= r.y1 && r.x1 <= nbx[i] && r.y1 <= nby[i], "rect %d of level %d: %d %d %d %d in a grid of %d x %d", k, i, r.x0, r.y0, r.x1, r.y1, nbx[i], nby[i]);
+        }
+        for (int gy = 0; gy < nby[i]; gy++)
+            for (int gx = 0; gx < nbx[i]; gx++) {
+                if (!must[i][(size_t)gy * nbx[i] + gx]) continue;
+                bool in = false;
+                for (int k = 0; k < P.nrect[i]; k++) in = in || (gx >= P.rects[i][k].x0 && gx < P.rects[i][k].x1 && gy >= P.rects[i][k].y0 && gy < P.rects[i][k].y1);
+                CHECK(in, "level %d block (%d, %d) is needed and lies in no rectangle (tx %d ty %d L %d)", i, gx, gy, tx, ty, L);
+                n_must++;
+            }
+    }
+    // blocks_run0: through the level-1 bitmap where the level-0 blocks pick themselves, else the union of the level-0 rectangles -- which the
+    // second plan (reach 0) must count in every case
+    if (P.need_n[1] > 0 && P.reach0 > 0) {
+        long n1 = 0; for (int v : model_bits1) n1 += v;
+        CHECK(P.blocks_run0 == std::min(4.0 * n1, (double)nbx[0] * nby[0]), "blocks_run0 %.0f through the bitmap, model %ld", P.blocks_run0, n1);
+        n_run_bitmap++;
+    }
+    LevelPlan& Q = g_plan2;
+    Q.reset();
+    Q.windows(pb, L, crows, ccols);
+    (void)Q.plan(table.data(), tx, ty, L, pb, cells, false, culled_any, 1, BH, 0);
+    long uni = 0;
+    for (int gy = 0; gy < nby[0]; gy++)
+        for (int gx = 0; gx < nbx[0]; gx++) {
+            bool in = false;
+            for (int k = 0; k < Q.nrect[0]; k++) in = in || (gx >= Q.rects[0][k].x0 && gx < Q.rects[0][k].x1 && gy >= Q.rects[0][k].y0 && gy < Q.rects[0][k].y1);
+            uni += in;
+        }
+    CHECK(Q.blocks_run0 == (double)uni, "blocks_run0 %.0f, union of the rectangles %ld (tx %d ty %d L %d)", Q.blocks_run0, uni, tx, ty, L);
+    n_union++;
+    double share[kMaxLevels]; int r0;
+    Q.run_shares(tx * ty, true, share, &r0);
+    for (int i = 0; i < L; i++) CHECK(share[i] > 0 && share[i] <= 1.0, "run share of level %d: %g", i, share[i]);
+}
+
+static void level_plan_checks()
+{
+    struct Shape { int tx, ty, Bc, only_L; } shapes[] = { { 2, 2, 8, 0 }, { 5, 3, 8, 0 }, { 5, 3, 1, 0 }, { 32, 2, 8, 0 }, { 32, 2, 2, 0 }, { 33, 2, 8, 0 }, { 33, 2, 3, 0 }, { 21, 21, 8, 2 }, { 9, 9, 1, 0 } };
+    const int Ls[4] = { 1, 2, 5, 7 };
+    for (const Shape& s : shapes)
+        for (int L : Ls) {
+            if (s.only_L && L != s.only_L) continue;
+            for (int pat = 0; pat < 7; pat++) {
+                Canvas c{ s.tx, s.ty, L, s.Bc, std::vector<int>((size_t)s.tx * s.ty, 1), std::vector<unsigned>((size_t)s.tx * s.ty, 0) };
+                const int n = s.tx * s.ty;
+                if (pat == 1) { for (int t = 0; t < n; t++) c.present[t] = 0; c.present[n - 1] = 1; c.out[n - 1] = 0x7fffu; }      // one rendered cell, in a corner
+                if (pat == 2) c.out[n / 2] = 1u << 5;                                                                              // one culled cell
+                if (pat >= 3)
+                    for (int t = 0; t < n; t++) {
+                        const unsigned r = rnd() % 10;
+                        c.present[t] = r >= (unsigned)pat - 2;                        // patterns 3 .. 6: ever fewer tiles
+                        c.out[t] = r % 3 == 0 ? 0 : (rnd() & 0xffffu);
+                        if (c.out[t] == 0xffffu) c.present[t] = 0;
+                    }
+                check_canvas(c);
+            }
+        }
+    // a level at which nothing is needed gets the single empty rectangle: a rendered tile and no hash cell
+    uint64_t one = 0x1000;
+    CellList none;
+    LevelPlan& P = g_plan;
+    P.reset();
+    P.windows(Win{ 0, 256, 0, 256 }, 5, 256, 256);
+    CHECK(P.plan(&one, 1, 1, 5, Win{ 0, 256, 0, 256 }, none, true, false, 1, BH, 0), "sharded plan");
+    for (int i = 0; i < 5; i++) { CHECK(P.nrect[i] == 1 && P.rects[i][0].x1 == 0 && P.rects[i][0].y1 == 0, "empty rectangle at level %d", i); n_empty_rect++; }
+    CHECK(P.blocks_run0 == 0, "blocks_run0 of empty rectangles");
+}
+
+// ------------------------------------------------------------------------------------------------ (e) - (g): the cull's bounds
+static long n_out, n_in, n_wmin_pos, n_wmin_zero, n_samples, n_frame_ok, n_frame_bad, n_raise_tiles, n_raised, n_tile_fresh, n_tile_whole, n_tile_partial, n_tile_pre;
+
+static long double radial_weight(long double sx, long double sy, int cols, int rows, int weight_type)      // MultiBandMap2DCPU.cpp:396-418 at the nearest pixel
+{
+    const long j = std::lround(sx), i = std::lround(sy);
+    if (j < 0 || i < 0 || j >= cols || i >= rows) return 0;
+    const long double xc = cols / 2, yc = rows / 2, dmax = std::sqrt(xc * xc + yc * yc);
+    long double w = 1 - std::sqrt((i - yc) * (i - yc) + (j - xc) * (j - xc)) / dmax;
+    if (weight_type != 0) w = w * w;
+    return w <= 1e-5L ? 1e-5L : w;
+}
+
+static void cull_checks()
+{
+    const int cols = 640, rows = 480, tx = 4, ty = 3, crows = ty * 256, ccols = tx * 256;
+    const double rot = 0.52359877559829887;       // 30 degrees
+    const double A[3][4] = { { 0.7, 0, 0, 0.7 }, { 0.7 * std::cos(rot), -0.7 * std::sin(rot), 0.7 * std::sin(rot), 0.7 * std::cos(rot) }, { 0.75, 0.05, -0.04, 0.7 } };
+    const double G[3][2] = { { 0, 0 }, { 0, 0 }, { 1.0e-4, -6.0e-5 } };                    // the third: mild perspective
+    const double centre[3][2] = { { 497, 359 }, { 512, 300 }, { -300, -200 } };             // the frame centre on the canvas: inside a cell, on a cell edge, outside the canvas
+    const float wlbs[5] = { -1.f, 1e-5f, 0.2f, 0.6f, 0.95f };
+    const int dils[3] = { 0, 1, 4 };
+    for (int h = 0; h < 3; h++)
+        for (int ci = 0; ci < 3; ci++) {
+            // source = A (p - c) / (1 + g . (p - c)) + (320, 240)
+            const double cx = centre[ci][0], cy = centre[ci][1], g0 = G[h][0], g1 = G[h][1], W0 = 1 - g0 * cx - g1 * cy;
+            const double M[9] = { A[h][0] + 320 * g0, A[h][1] + 320 * g1, -A[h][0] * cx - A[h][1] * cy + 320 * W0,
+                                  A[h][2] + 240 * g0, A[h][3] + 240 * g1, -A[h][2] * cx - A[h][3] * cy + 240 * W0, g0, g1, W0 };
+            CHECK(cull_frame_ok(M, crows, ccols), "tame map %d %d", h, ci); n_frame_ok++;
+            for (int di = 0; di < 3; di++)
+                for (int wt = 0; wt < 2; wt++) {
+                    const int dil = dils[di]; const bool single = dil == 0;
+                    Lattice lat, part;
+                    lat.map_canvas(M, crows, ccols, cols, rows, dil, true, CullMargins());
+                    part.map_canvas(M, crows, ccols, cols, rows, dil, false, CullMargins());      // points mapped on first use: the same answers
+                    for (int span = 1; span <= 4; span += 3)
+                        for (int m = 0; m + span <= 4 * ty; m += span)
+                            for (int k = 0; k + span <= 4 * tx; k += span) {
+                                long double smin = 2, smax = -1; bool corners_in = true;
+                                for (int iy = 0; iy <= 32; iy++)
+                                    for (int ix = 0; ix <= 32; ix++) {
+                                        const long double x = 64.0L * (k - dil) + 64.0L * (span + 2 * dil) * ix / 32, y = 64.0L * (m - dil) + 64.0L * (span + 2 * dil) * iy / 32;
+                                        const long double W = M[6] * x + M[7] * y + M[8], sx = (M[0] * x + M[1] * y + M[2]) / W, sy = (M[3] * x + M[4] * y + M[5]) / W;
+                                        const long double w = radial_weight(sx, sy, cols, rows, wt);
+                                        smin = std::min(smin, w); smax = std::max(smax, w);
+                                        if ((ix % 32 == 0) && (iy % 32 == 0) && w == 0) corners_in = false;
+                                        n_samples++;
+                                    }
+                                for (float wl : wlbs) {
+                                    const float bound = stored_bound(wl, single);
+                                    float wmin = -5.f, wmin2 = -5.f;
+                                    const bool out = lat.cell_out(k, m, span, wt, bound, true, &wmin);
+                                    CHECK(out == part.cell_out(k, m, span, wt, bound, true, &wmin2) && wmin == wmin2, "lattice mapped at once and on first use differ at (%d, %d)", k, m);
+                                    if (out) CHECK(smax < (long double)bound, "cell (%d, %d) span %d dil %d type %d map %d/%d is out against %g and has weight %Lg", k, m, span, dil, wt, h, ci, bound, smax);
+                                    CHECK((long double)wmin <= smin && wmin >= 0.f, "wmin %g above a sampled weight %Lg at (%d, %d) span %d dil %d type %d map %d/%d", wmin, smin, k, m, span, dil, wt, h, ci);
+                                    CHECK(wmin == 0.f || corners_in, "wmin %g with a corner outside the frame", wmin);
+                                    CHECK(!lat.cell_out(k, m, span, wt, bound, false, nullptr), "want_out false");
+                                    (out ? n_out : n_in)++; (wmin > 0 ? n_wmin_pos : n_wmin_zero)++;
+                                }
+                            }
+                    // (f) both routes of raise_bounds: the same bits in every tile (4 x 4 cells, every point mapped)
+                    {
+                        for (int start = 0; start < 2; start++)
+                            for (int y = 0; y < ty; y++)
+                                for (int x = 0; x < tx; x++) {
+                                    float a[16], b[16];
+                                    for (int q = 0; q < 16; q++) a[q] = b[q] = start ? wlbs[rnd() % 5] : -1.f;
+                                    float before[16]; std::memcpy(before, a, sizeof a);
+                                    lat.raise_bounds_fast(x, y, wt, a); lat.raise_bounds_cells(x, y, wt, b);
+                                    CHECK(std::memcmp(a, b, sizeof a) == 0, "raise_bounds: the two routes differ in tile (%d, %d) dil %d type %d map %d/%d", x, y, dil, wt, h, ci);
+                                    for (int q = 0; q < 16; q++) { CHECK(a[q] >= before[q], "a bound fell"); n_raised += a[q] > before[q]; }
+                                    float c2[16]; std::memcpy(c2, before, sizeof c2);
+                                    lat.raise_bounds(x, y, wt, c2);
+                                    CHECK(std::memcmp(a, c2, sizeof a) == 0, "raise_bounds' own choice of route");
+                                    n_raise_tiles++;
+                                }
+                    }
+                    // (g) the per-tile decision against what the per-cell answers imply
+                    for (int y = 0; y < ty; y++)
+                        for (int x = 0; x < tx; x++)
+                            for (int v = 0; v < 24; v++) {
+                                const bool fresh = v & 1, lookahead = v & 2, pre = (v & 4) != 0;
+                                float wl[16];
+                                for (int q = 0; q < 16; q++) wl[q] = v < 8 ? wlbs[2 + v % 3] : wlbs[rnd() % 5];
+                                float lo = wl[0]; for (int q = 1; q < 16; q++) lo = std::min(lo, wl[q]);
+                                const bool ask = !fresh || lookahead, whole = ask && lat.cell_out(4 * x, 4 * y, 4, wt, stored_bound(lo, single), true, nullptr);
+                                unsigned expect = 0;
+                                for (int q = 0; q < 16; q++)
+                                    if (whole || (ask && lat.cell_out(4 * x + q % 4, 4 * y + q / 4, 1, wt, stored_bound(wl[q], single), true, nullptr))) expect |= 1u << q;
+                                if (fresh && expect != 0xffffu) expect = 0;
+                                TileCull tc;
+                                lat.tile_cull(x, y, wl, fresh, lookahead, pre, wt, single, tc);
+                                CHECK(tc.out == expect, "tile_cull (%d, %d): %04x, the cells imply %04x (fresh %d lookahead %d pre_raised %d)", x, y, tc.out, expect, fresh, lookahead, pre);
+                                if (fresh && !lookahead) CHECK(tc.out == 0, "a fresh tile without lookahead");
+                                if (fresh) { CHECK(tc.out == 0 || tc.out == 0xffffu, "a fresh tile in part"); n_tile_fresh++; }
+                                if (pre && whole) { CHECK(tc.out == 0xffffu && tc.nraise == 0, "pre_raised, whole tile out"); n_tile_pre++; }
+                                for (int r = 0; r < tc.nraise; r++) {
+                                    float wmin; (void)lat.cell_out(4 * x + tc.q[r] % 4, 4 * y + tc.q[r] / 4, 1, wt, stored_bound(wl[tc.q[r]], single), false, &wmin);
+                                    CHECK(tc.w[r] == (pre ? 0.f : wmin) && tc.w[r] > wl[tc.q[r]], "raise of cell %d", tc.q[r]);      // (pre_raised: the bounds are not worked out again)
+                                }
+                                if (tc.out == 0xffffu) n_tile_whole++; else if (tc.out) n_tile_partial++;
+                            }
+                }
+        }
+    // W changes sign across the canvas: no cull
+    const double bad[9] = { 0.7, 0, 10, 0, 0.7, 10, 1.0 / 400, 0, -1 };
+    CHECK(!cull_frame_ok(bad, crows, ccols), "a map whose W changes sign"); n_frame_bad++;
+}
+
+int main()
+{
+    level_plan_checks();
+    cull_checks();
+    std::printf("plan: bitmaps %ld bits_set %ld bits_clear %ld no_bitmap_wide %ld no_bitmap_big %ld overflow %ld exact %ld exact_blocks %ld windows %ld regions %ld "
+                "rect_plans %ld merge0 %ld mergeU %ld must %ld empty_rect %ld union %ld run_bitmap %ld\n",
+                n_bitmaps, n_bits_set, n_bits_clear, n_no_bitmap_wide, n_no_bitmap_big, n_overflow, n_exact, n_exact_blocks, n_windows, n_regions,
+                n_rect_plans, n_merge0, n_mergeU, n_must, n_empty_rect, n_union, n_run_bitmap);
+    std::printf("cull: out %ld in %ld wmin_pos %ld wmin_zero %ld samples %ld frame_ok %ld frame_bad %ld raise_tiles %ld raised %ld "
+                "tile_fresh %ld tile_whole %ld tile_partial %ld tile_pre %ld\n",
+                n_out, n_in, n_wmin_pos, n_wmin_zero, n_samples, n_frame_ok, n_frame_bad, n_raise_tiles, n_raised, n_tile_fresh, n_tile_whole, n_tile_partial, n_tile_pre);
+    std::printf("frame plan ok\n");
+    return 0;
+}
