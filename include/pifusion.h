@@ -130,6 +130,14 @@ int     pf_save(pf_map* m, const char* filename);
  * tile; row-major 4 x 4, z = 0).  Multi-band maps: overview chain, empty test and tile encode run on the GPU on the mosaic where the
  * collapse left it (csrc/overview.hip, jpeg_encode.hip); only flags, offsets and streams cross to the host.  Any file name.  */
 int     pf_save_tiff(pf_map* m, const char* filename, int quality, int force_bigtiff);
+/* pf_save_tiff with a transparency mask behind every image: the file is pf_tiff_write_bgr_masked(filename, bgr, ..., mask, ...,
+ * quality, Result.BackGroundColor, T, force_bigtiff) of the bgr and mask pf_save_to_memory_mask returns and pf_save_tiff's T.
+ * Covered = the level-0 weight of the pixel is not 0 (exactly where save() does not paint the background); tile slots of the
+ * bounding box without a map tile are not covered.  Multi-band maps: the masks come from the weights where they lie in HBM
+ * (csrc/coverage.hip, k_coverage_tiles, on the table the collapse uses) under the same hold of the map as the collapse.
+ * Single-band maps: the host writer, covered = the tile's alpha byte (the winning weight) is not 0.  A map without content
+ * returns 0.  pf_save never writes this file: ".tif" stays unmasked.                                                     */
+int     pf_save_tiff_masked(pf_map* m, const char* filename, int quality, int force_bigtiff);
 /* The file leg of save() alone: cv::imwrite(filename, result), MultiBandMap2DCPU.cpp:841.  8-bit BGR in,
  * PNG (8-bit RGB, deflate) when the name ends in .png/.PNG, JPEG (pf_jpeg_encode_bgr at quality 95) when it ends in
  * .jpg/.jpeg in either case, the pyramid TIFF (pf_tiff_write_bgr at quality 95, background 0, no geo tags) when it ends in
@@ -164,6 +172,35 @@ int     pf_tiff_write_bgr(const char* filename, const uint8_t* bgr, int rows, in
  * and streams cross to the host, pixels do not.  The counterpart of pf_jpeg_encode_device; returns when the file is written. */
 int     pf_tiff_write_device(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, int quality, int bg,
                              const double model_transform[16], int force_bigtiff, void* hip_stream);
+/* The masked pyramid TIFF: the file of pf_tiff_write_bgr for the same pixels, quality, bg, model_transform and force_bigtiff, plus a
+ * TIFF 6.0 transparency mask behind every image, so that a reader can tell "no data" from a pixel of the background colour.
+ *   masks    mask: a byte per pixel, non-zero = covered, `mask_step` bytes per row (0 = packed).  M_0[y, x] = 1 where the pixel is
+ *            covered; M_k+1[y, x] = the OR of the 2 x 2 block of M_k, a missing last row or column repeating the one before it
+ *            (the geometry of the colour chain): a pixel of an overview is opaque if any pixel under it is.
+ *   IFDs     chained image 0, mask 0, image 1, mask 1, ...; the colour IFDs carry the tags of the unmasked file.  A mask IFD
+ *            (tags sorted): NewSubfileType (254) 4 for mask 0 and 5 for the others, ImageWidth / ImageLength of its image,
+ *            BitsPerSample 1 (count 1), Compression 1, Photometric 4 (transparency mask), SamplesPerPixel 1,
+ *            PlanarConfiguration 1, TileWidth / TileLength 256, TileOffsets, TileByteCounts (every entry 8192).  No FillOrder: the
+ *            default, most significant bit first, holds.
+ *   tiles    a mask tile is 256 rows of 32 bytes, uncompressed; bit 7 of byte 0 is column 0; bits past the image are 0.
+ *   sharing  the mask tiles whose 65 536 bits are all 0 are stored once, those whose bits are all 1 are stored once, every other
+ *            mask tile on its own.  The colour streams, the colour empty test and the shared empty stream are the unmasked file's.
+ *   layout   header; all IFDs with their out-of-line values, in chain order; the shared empty stream, if any; the shared all-zero
+ *            mask tile, if any; the shared all-one mask tile, if any; the colour streams, image by image; the other mask tiles,
+ *            image by image, row-major.  Everything starts on an even offset; classic TIFF unless the file needs BigTIFF or
+ *            force_bigtiff is set.  (tiff::layout_as again: with no mask it places the bytes of pf_tiff_write_bgr.)
+ * Host code, no device.  0 + pf_last_error() on failure (no name, image or mask, a step smaller than a row, a file that cannot be
+ * written), and no file is left behind.                                                                                    */
+int     pf_tiff_write_bgr_masked(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step,
+                                 const uint8_t* mask, size_t mask_step, int quality, int bg,
+                                 const double model_transform[16], int force_bigtiff);
+/* The same file, byte for byte, from an image and a mask (a byte per pixel) of any size in device memory: pf_tiff_write_device with
+ * the masks made beside the colour chain (csrc/coverage.hip: k_coverage_bytes packs level 0, k_mask_overview ORs every further
+ * level from the bit plane above, per-tile "all zero" / "all one" flags travel with the colour flags); only the mask tiles that
+ * are neither are gathered and cross to the host, no plane does.  Refuses what pf_tiff_write_device refuses. */
+int     pf_tiff_write_device_masked(const char* filename, const void* dev_bgr, int rows, int cols, size_t step,
+                                    const void* dev_mask, size_t mask_step, int quality, int bg,
+                                    const double model_transform[16], int force_bigtiff, void* hip_stream);
 /* cv::imencode(".jpg") / the JPEG leg of cv::imwrite of OpenCV 2.4.9: baseline JPEG, byte for byte what libjpeg writes after
  * jpeg_set_defaults, JCS_RGB input and jpeg_set_quality(quality, TRUE) -- JFIF 1.01, 4:2:0, the Annex K tables, one interleaved
  * scan, integer colour conversion and ISLOW DCT.  bgr: rows x cols 8-bit BGR, `step` bytes per row (0 = packed).  quality is
@@ -205,6 +242,9 @@ int     pf_feed_jpeg_batch(pf_map* m, int n, const uint8_t* const* data, const s
 /* save() without the file: whole-mosaic collapse into caller memory.  Call
  * with bgr=NULL to query rows/cols/origin tile.                            */
 int     pf_save_to_memory(pf_map* m, uint8_t* bgr, int* rows, int* cols, int* tile_x0, int* tile_y0);
+/* The mosaic and its coverage of ONE moment: bgr as pf_save_to_memory gives it, mask rows x cols bytes, 255 where weights[0] != 0,
+ * else 0.  bgr == NULL && mask == NULL: the extent alone.  Either of the two may be NULL once the extent is known.       */
+int     pf_save_to_memory_mask(pf_map* m, uint8_t* bgr, uint8_t* mask, int* rows, int* cols, int* tile_x0, int* tile_y0);
 
 /* --- MultiBandMap2DCPU::Ele tile surface (MultiBandMap2DCPU.h:32-51) ---- */
 int     pf_num_levels(pf_map* m);                        /* bandNum+1          */

@@ -157,6 +157,8 @@ public:
     // .png, .jpg / .jpeg, .tif / .tiff (tiled pyramid TIFF with JPEG tiles, overviews and geo tags), else PPM: see pf_save
     bool save(const std::string& filename) { return pf_save(h_, filename.c_str()) != 0; }
     bool saveTiff(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
+    // the pyramid TIFF with a transparency mask behind every image: covered where the level-0 weight is not 0 (pf_save_tiff_masked)
+    bool saveMasked(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff_masked(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
     unsigned queueSize() { return pf_queue_size(h_); }
     bool sync() { return pf_sync(h_) != 0; }
 

@@ -112,6 +112,11 @@ def lib():
         L.pf_tiff_write_bgr.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, dp, C.c_int]
         L.pf_tiff_write_device.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, dp, C.c_int, vp]
         L.pf_save_tiff.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
+    if hasattr(L, "pf_tiff_write_bgr_masked") or not os.environ.get("PF_LIB"):
+        L.pf_tiff_write_bgr_masked.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, dp, C.c_int]
+        L.pf_tiff_write_device_masked.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, dp, C.c_int, vp]
+        L.pf_save_tiff_masked.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
+        L.pf_save_to_memory_mask.argtypes = [vp, vp, vp, ip, ip, ip, ip]
     L.pf_debug_jpeg_huffman.argtypes = [vp, C.POINTER(C.c_longlong)]; L.pf_debug_jpeg_huffman.restype = None
     L.pf_feed_jpeg_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), dp, C.c_int, ip]
     L.pf_num_levels.argtypes = [vp]
@@ -339,6 +344,30 @@ def tiff_write_device(filename, dev_ptr, rows, cols, quality=95, bg=0, model_tra
     return bool(lib().pf_tiff_write_device(filename.encode(), dev_ptr, rows, cols, step, quality, bg, xf, int(force_bigtiff), stream))
 
 
+def tiff_write_masked(filename, bgr, mask, quality=95, bg=0, model_transform=None, force_bigtiff=False):
+    """tiff_write with a transparency mask behind every image (pf_tiff_write_bgr_masked): mask is HxW, non-zero = covered (rows may be
+    padded); every overview's mask is the OR of the 2 x 2 blocks of the one above.  Host code."""
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(bgr, dtype=np.uint8)
+    m = np.asarray(mask)
+    if m.dtype == np.bool_:
+        m = m.astype(np.uint8)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3 or m.shape != a.shape[:2]:
+        raise ValueError("tiff_write_masked: HxWx3 and HxW expected")
+    keep, xf = _transform16(model_transform)
+    return bool(lib().pf_tiff_write_bgr_masked(filename.encode(), a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], m.ctypes.data, m.strides[0],
+                                               quality, bg, xf, int(force_bigtiff)))
+
+
+def tiff_write_device_masked(filename, dev_ptr, rows, cols, dev_mask, quality=95, bg=0, model_transform=None, force_bigtiff=False, step=0, mask_step=0, stream=None):
+    """The same file, byte for byte, from pixels and a byte-per-pixel mask at device addresses (csrc/coverage.hip beside overview.hip)."""
+    keep, xf = _transform16(model_transform)
+    return bool(lib().pf_tiff_write_device_masked(filename.encode(), dev_ptr, rows, cols, step, dev_mask, mask_step, quality, bg, xf, int(force_bigtiff), stream))
+
+
 def jpeg_huffman_counts(map2d=None):
     """(frames whose Huffman pass ran on the GPU, frames that fell back to the host after trying, rounds of the most recent GPU pass) of a map's
     decoder, or of decode_jpeg_device's when map2d is None"""
@@ -459,6 +488,24 @@ class Map2D:
     def save_tiff(self, filename, quality=95, force_bigtiff=False):
         """save("x.tif") with the tiles' JPEG quality and the flag that forces BigTIFF (pf_save_tiff)"""
         return bool(lib().pf_save_tiff(self._h, filename.encode(), quality, int(force_bigtiff)))
+
+    def save_tiff_masked(self, filename, quality=95, force_bigtiff=False):
+        """save_tiff with a transparency mask behind every image: covered where the level-0 weight is not 0 (pf_save_tiff_masked)"""
+        return bool(lib().pf_save_tiff_masked(self._h, filename.encode(), quality, int(force_bigtiff)))
+
+    def save_to_memory_mask(self):
+        """(mosaic BGR8, coverage HxW uint8: 255 where the level-0 weight is not 0, (tile x0, tile y0)) of one moment"""
+        r, c, x0, y0 = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        if not lib().pf_save_to_memory_mask(self._h, None, None, C.byref(r), C.byref(c), C.byref(x0), C.byref(y0)):
+            return None
+        # (the extent may have grown between the two calls: the second call fills what it reports, so it is asked until it fits)
+        while True:
+            out = np.empty((r.value, c.value, 3), np.uint8); mask = np.empty((r.value, c.value), np.uint8)
+            want = (r.value, c.value)
+            if not lib().pf_save_to_memory_mask(self._h, out.ctypes.data, mask.ctypes.data, C.byref(r), C.byref(c), C.byref(x0), C.byref(y0)):
+                return None
+            if (r.value, c.value) == want:
+                return out, mask, (x0.value, y0.value)
 
     def save_to_memory(self, alloc=None):
         """(mosaic BGR8, (tile x0, tile y0)); alloc(shape) -> uint8 array supplies the buffer (e.g. host_array)."""

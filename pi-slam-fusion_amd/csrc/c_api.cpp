@@ -92,6 +92,7 @@ unsigned pf_queue_size(pf_map* m) { return m ? m->impl.queue_size() : 0; }
 int pf_sync(pf_map* m) { return m && m->impl.sync(); }
 int pf_save(pf_map* m, const char* filename) { return m && filename && m->impl.save(filename); }
 int pf_save_tiff(pf_map* m, const char* filename, int quality, int force_bigtiff) { return m && filename && m->impl.save_tiff(filename, quality, force_bigtiff != 0); }
+int pf_save_tiff_masked(pf_map* m, const char* filename, int quality, int force_bigtiff) { return m && filename && m->impl.save_tiff_masked(filename, quality, force_bigtiff != 0); }
 // pf_write_image / pf_image_info / pf_read_image: image_io.cpp (host code without a HIP dependency: also built by the sanitizer targets)
 int pf_jpeg_info(const uint8_t* data, size_t len, int* rows, int* cols, int* components) { return pf::jpeg_info(data, len, rows, cols, components); }
 int pf_jpeg_decode_bgr(const uint8_t* data, size_t len, uint8_t* bgr, int rows, int cols)
@@ -168,6 +169,28 @@ int pf_tiff_write_device(const char* filename, const void* dev_bgr, int rows, in
     if (at.device != prev) (void)hipSetDevice(prev);
     return ok;
 }
+int pf_tiff_write_device_masked(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, const void* dev_mask, size_t mask_step, int quality, int bg,
+                                const double model_transform[16], int force_bigtiff, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_jpeg_mu);
+    if (!filename || !dev_bgr || !dev_mask || rows <= 0 || cols <= 0) { pf::set_error("pf_tiff_write_device_masked: no name, no image, no mask or a size that is not positive"); return 0; }
+    if (step == 0) step = (size_t)cols * 3;
+    if (mask_step == 0) mask_step = (size_t)cols;
+    if (step < (size_t)cols * 3 || mask_step < (size_t)cols) { pf::set_error("pf_tiff_write_device_masked: step is smaller than a row"); return 0; }
+    hipPointerAttribute_t at{}, am{};
+    if (hipPointerGetAttributes(&at, dev_bgr) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_tiff_write_device_masked: the image is not in device memory"); return 0; }
+    if (hipPointerGetAttributes(&am, dev_mask) != hipSuccess || am.type != hipMemoryTypeDevice || am.device != at.device) {
+        (void)hipGetLastError(); pf::set_error("pf_tiff_write_device_masked: the mask is not in device memory beside the image"); return 0;
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_tiff_write_device_masked: hipSetDevice failed"); return 0; }
+    pf::TiffDevice::Mask mk;
+    mk.dev_bytes = dev_mask; mk.step = mask_step;
+    const int ok = shared_tiff_device(at.device)->write(filename, dev_bgr, rows, cols, step, quality, bg, model_transform, force_bigtiff != 0, *shared_jpeg_encoder(at.device), hip_stream, &mk);
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
 void pf_debug_jpeg_huffman(pf_map* m, long long out[3])
 {
     if (!out) return;
@@ -215,6 +238,9 @@ int pf_feed_jpeg_batch(pf_map* m, int n, const uint8_t* const* data, const size_
 }
 int pf_save_to_memory(pf_map* m, uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
 { return m && rows && cols && tx0 && ty0 && m->impl.save_to_memory(bgr, rows, cols, tx0, ty0); }
+
+int pf_save_to_memory_mask(pf_map* m, uint8_t* bgr, uint8_t* mask, int* rows, int* cols, int* tx0, int* ty0)
+{ return m && rows && cols && tx0 && ty0 && m->impl.save_to_memory_mask(bgr, mask, rows, cols, tx0, ty0); }
 
 int pf_num_levels(pf_map* m) { return m ? m->impl.num_levels() : 0; }
 int pf_pyramid_type(pf_map* m) { return m ? m->impl.pyramid_type() : 0; }

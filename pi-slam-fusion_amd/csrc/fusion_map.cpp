@@ -3,6 +3,7 @@
 #include "fusion_map.hpp"
 #include "env.hpp"
 #include "warp_index.hpp"
+#include "coverage.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -231,6 +232,7 @@ FusionMap::~FusionMap()
     if (out_ready_) (void)hipEventDestroy(out_ready_);
     if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
     blend_src_.release(); blend_out_raw_.release(); blend_out_bgr_.release(); mosaic_table_.release(); w8_.release(); wmap_.release();
+    cover_plane_.release(); cover_bytes_.release();
     jpeg_enc_.release(); tiff_dev_.release();
     store_.clear();
     (void)hipStreamDestroy(stream_);
@@ -1922,19 +1924,24 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
     const bool file = t.kind == SaveTarget::File;
     if (file && single_band_) { set_error("save: the stream of a mosaic in HBM was asked for where there is none"); return false; }
     if (file && t.route == SaveRoute::DeviceJpeg && !jpeg_size_ok("save", t.rows, t.cols)) return false;          // before anything is made: no file
-    const size_t out_bytes = (size_t)t.rows * t.cols * 3;
-    if (t.kind == SaveTarget::Image) t.image->resize(out_bytes);
+    const size_t out_bytes = (size_t)t.rows * t.cols * 3, mask_bytes = (size_t)t.rows * t.cols;
+    if (t.kind == SaveTarget::Image) { t.image->resize(out_bytes); if (t.mask_image) t.mask_image->resize(mask_bytes); }
     uint8_t* const bgr = file ? nullptr : t.kind == SaveTarget::Image ? t.image->data() : t.bgr;
+    uint8_t* const mask = file ? nullptr : t.kind == SaveTarget::Image ? (t.mask_image ? t.mask_image->data() : nullptr) : t.mask;
     if (single_band_) {          // Map2DCPU::save (Map2DCPU.cpp:523-563): paste the tiles; holes are zero here
         HIP_OK(sync_all());
-        std::memset(bgr, 0, out_bytes);
+        if (bgr) std::memset(bgr, 0, out_bytes);
+        if (mask) std::memset(mask, 0, mask_bytes);          // covered: the tile's alpha byte, the winning weight, is not 0
         std::vector<uint8_t> px((size_t)kElePixels * kElePixels * 4);
         bool ok = true;
         store_.for_each([&](int ix, int iy, Tile& tile) {
             if (tile.fresh || !ok) return;
             if (hipMemcpy(px.data(), tile.base, px.size(), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; return; }
-            for (int r = 0; r < kElePixels; r++)
-                bgra_to_bgr(px.data() + (size_t)r * kElePixels * 4, bgr + (((size_t)(iy - mny) * kElePixels + r) * t.cols + (size_t)(ix - mnx) * kElePixels) * 3, kElePixels);
+            for (int r = 0; r < kElePixels; r++) {
+                const size_t o = ((size_t)(iy - mny) * kElePixels + r) * t.cols + (size_t)(ix - mnx) * kElePixels;
+                if (bgr) bgra_to_bgr(px.data() + (size_t)r * kElePixels * 4, bgr + o * 3, kElePixels);
+                if (mask) for (int x = 0; x < kElePixels; x++) mask[o + x] = px[((size_t)r * kElePixels + x) * 4 + 3] ? 255 : 0;
+            }
         });
         return ok;
     }
@@ -1949,7 +1956,7 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
     if (!blend_out_bgr_.reserve(out_bytes)) return false;
 #if PF_EXPERIMENTS
     static const bool per_level = exp_env("PF_BLEND_PER_LEVEL") != nullptr;
-    if (per_level) {                              // rounds 1-5: paste per level, one collapse launch per level, finish
+    if (per_level && bgr && !mask) {                              // rounds 1-5: paste per level, one collapse launch per level, finish
         for (int i = 0; i <= L; i++) {
             const size_t n = (size_t)(t.rows >> i) * (t.cols >> i);
             if (!blend_lv_[i].reserve(n * px)) return false;
@@ -1972,38 +1979,58 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
 #endif
     // one launch: paste, collapse in LDS, 8U, background (collapse_fused.hip).  Algorithmic bytes: every tile's Laplacians and
     // level-0 weights read once, the mosaic written once.
-    double P = 0; for (int i = 0; i <= L; i++) P += 1.0 / (double)(1 << (2 * i));
-    prof_begin(K_SAVE_FUSED, (double)cnt * kElePixels * kElePixels * (P * px + 4) + (double)out_bytes);
-    launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
-    prof_end();
-    HIP_OK(hipGetLastError());
-    if (!file) return download({ { bgr, blend_out_bgr_.p, out_bytes } });
+    if (file || bgr) {
+        double P = 0; for (int i = 0; i <= L; i++) P += 1.0 / (double)(1 << (2 * i));
+        prof_begin(K_SAVE_FUSED, (double)cnt * kElePixels * kElePixels * (P * px + 4) + (double)out_bytes);
+        launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
+        prof_end();
+        HIP_OK(hipGetLastError());
+    }
+    if (!file) {
+        std::vector<OutPiece> pieces;
+        if (bgr) pieces.push_back({ bgr, blend_out_bgr_.p, out_bytes });
+        if (mask) {          // the coverage from the same table: the weights' "!= 0" bits (coverage.hip), spread to bytes for the caller
+            if (!cover_plane_.reserve(mask_bytes / 8) || !cover_bytes_.reserve(mask_bytes)) return false;
+            launch_coverage_tiles(stream_, (const uint64_t*)mosaic_table_.p, wx, wy, lay_.w_off[0], (uint8_t*)cover_plane_.p, nullptr, nullptr);
+            launch_coverage_expand(stream_, (const uint8_t*)cover_plane_.p, t.rows, t.cols, (uint8_t*)cover_bytes_.p);
+            HIP_OK(hipGetLastError());
+            pieces.push_back({ mask, cover_bytes_.p, mask_bytes });
+        }
+        return download(pieces);
+    }
     // the mosaic stays where the collapse left it
-    if (t.route == SaveRoute::DeviceTiff)          // overviews, empty test and tile streams are made from it there
-        return tiff_dev_.write(t.name, blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, t.quality, opt_.bg_color, t.transform, t.force_bigtiff, jpeg_enc_, stream_);
+    if (t.route == SaveRoute::DeviceTiff) {        // overviews, empty test and tile streams are made from it there; the masks from the table
+        TiffDevice::Mask mk;
+        mk.dev_table = (const uint64_t*)mosaic_table_.p; mk.wx = wx; mk.wy = wy; mk.w_off = lay_.w_off[0];
+        return tiff_dev_.write(t.name, blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, t.quality, opt_.bg_color, t.transform, t.force_bigtiff, jpeg_enc_, stream_,
+                               t.masked ? &mk : nullptr);
+    }
     size_t off[2];                                 // cv::imwrite's JPEG defaults: quality 95, 4:2:0
     if (!jpeg_enc_.encode(blend_out_bgr_.p, 1, nullptr, 0, t.rows, t.cols, (size_t)t.cols * 3, t.quality, off, stream_)) return false;
     const uint8_t* stream = jpeg_enc_.fetch_pinned(stream_);
     return stream && write_bytes_file(t.name, stream, off[1]);
 }
 
-bool FusionMap::save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
+bool FusionMap::save_to_memory_mask(uint8_t* bgr, uint8_t* mask, int* rows, int* cols, int* tx0, int* ty0)
 {
     SaveTarget t;
-    t.kind = bgr ? SaveTarget::Buffer : SaveTarget::Extent; t.bgr = bgr;
+    t.kind = bgr || mask ? SaveTarget::Buffer : SaveTarget::Extent; t.bgr = bgr; t.mask = mask;
     if (!save_mosaic(t)) return false;
     *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
     return true;
 }
 
-bool FusionMap::save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign)
+bool FusionMap::save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign, bool masked)
 {
-    std::vector<uint8_t> img;
+    std::vector<uint8_t> img, cover;
     SaveTarget t;
-    if (route_on_device(route)) { t.kind = SaveTarget::File; t.name = filename; t.route = route; t.quality = quality; t.force_bigtiff = force_bigtiff; }
-    else { t.kind = SaveTarget::Image; t.image = &img; }
+    if (route_on_device(route)) { t.kind = SaveTarget::File; t.name = filename; t.route = route; t.quality = quality; t.force_bigtiff = force_bigtiff; t.masked = masked; }
+    else { t.kind = SaveTarget::Image; t.image = &img; if (masked) t.mask_image = &cover; }
     if (!save_mosaic(t, foreign)) return false;
-    if (route == SaveRoute::HostTiffGeo && !write_tiff_file("save", filename, img.data(), t.rows, t.cols, 0, quality, opt_.bg_color, t.transform, force_bigtiff)) return false;
+    if (route == SaveRoute::HostTiffGeo) {
+        if (masked ? !write_tiff_masked_file("save", filename, img.data(), t.rows, t.cols, 0, cover.data(), 0, quality, opt_.bg_color, t.transform, force_bigtiff)
+                   : !write_tiff_file("save", filename, img.data(), t.rows, t.cols, 0, quality, opt_.bg_color, t.transform, force_bigtiff)) return false;
+    }
     if (route == SaveRoute::HostImage && !write_image_file(filename, img.data(), t.rows, t.cols)) return false;
     std::printf("Resolution:[%d %d]\n", t.cols, t.rows);
     return true;

@@ -112,6 +112,8 @@ public:
     // and the flag that forces BigTIFF.  Both are save_file() with the route chosen
     bool save(const char* filename) { return save_file(filename, save_route(filename, single_band_), 95, false); }
     bool save_tiff(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff); }
+    // save_tiff() with a transparency mask behind every image (pf_save_tiff_masked): covered = the level-0 weight is not 0
+    bool save_tiff_masked(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff, nullptr, true); }
     struct ForeignTile { int ix, iy; const void* dev; };          // a tile slot image held outside the store (gathered for save)
     // Where the collapsed mosaic of one save goes.  A value: what the caller asks for, and what save_mosaic() found out on the way
     struct SaveTarget {
@@ -123,6 +125,11 @@ public:
         uint8_t* bgr = nullptr;
         std::vector<uint8_t>* image = nullptr;
         const char* name = nullptr; SaveRoute route = SaveRoute::HostImage; int quality = 95; bool force_bigtiff = false;
+        // the coverage of the same moment, rows * cols bytes, 255 where the level-0 weight is not 0: beside bgr (Buffer; either of
+        // the two may be null then), beside image (Image), or as the masks of the file (File, route DeviceTiff)
+        uint8_t* mask = nullptr;
+        std::vector<uint8_t>* mask_image = nullptr;
+        bool masked = false;
         // results
         int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
         double transform[16] = {};      // the ModelTransformationTag of a TIFF of this mosaic: pixel -> plane metres
@@ -131,9 +138,11 @@ public:
     // that take part without entering the store (dist.cpp)
     bool save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* foreign = nullptr);
     // save_mosaic() into the file: on the GPU, or as pixels through the route's host writer; prints the reference's "Resolution:" line
-    bool save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign = nullptr);
+    bool save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign = nullptr, bool masked = false);
     // the two-call protocol of pf_save_to_memory: bgr == nullptr reports the extent, bgr takes the pixels of the extent at that moment
-    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0);
+    bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0) { return save_to_memory_mask(bgr, nullptr, rows, cols, tx0, ty0); }
+    // ... with the coverage beside the pixels (pf_save_to_memory_mask): both null reports the extent, either may be null after that
+    bool save_to_memory_mask(uint8_t* bgr, uint8_t* mask, int* rows, int* cols, int* tx0, int* ty0);
 
     // seam exchange support (dist.cpp)
     using TileRec = pf::TileRec;        // dist_plan.hpp
@@ -363,6 +372,7 @@ private:
 
     // blend / save scratch (blend_lv_: the per-level form of the experiments library only)
     DevBuf blend_lv_[kMaxLevels], blend_src_, blend_out_raw_, blend_out_bgr_, mosaic_table_, strip_desc_;
+    DevBuf cover_plane_, cover_bytes_;          // pf_save_to_memory_mask: the mosaic's coverage as a bit plane (coverage.hip), and as bytes
     // results on their way to the host: two pinned staging slots, filled on copy_stream_ while the host empties the other one
     static constexpr size_t kOutSlot = (size_t)32 << 20;
     TiffDevice  tiff_dev_;      // save("x.tif"): level buffers and flags of its own, tiles through jpeg_enc_

@@ -150,6 +150,17 @@ bool write_tiff_file(const char* who, const char* filename, const uint8_t* bgr, 
     catch (const std::bad_alloc&) { std::remove(filename); set_error(std::string(who) + ": out of memory"); return false; }
 }
 
+bool write_tiff_masked_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                            int quality, int bg, const double* model_transform, bool force_bigtiff)
+{
+    if (!filename || !bgr || !mask || rows <= 0 || cols <= 0) { set_error(std::string(who) + ": no name, no image, no mask or a size that is not positive"); return false; }
+    if (step == 0) step = (size_t)cols * 3;
+    if (mask_step == 0) mask_step = (size_t)cols;
+    if (step < (size_t)cols * 3 || mask_step < (size_t)cols) { set_error(std::string(who) + ": step is smaller than a row"); return false; }
+    try { return tiff::write_bgr_masked(filename, bgr, rows, cols, step, mask, mask_step, quality, bg, model_transform, force_bigtiff); }
+    catch (const std::bad_alloc&) { std::remove(filename); set_error(std::string(who) + ": out of memory"); return false; }
+}
+
 bool jpeg_size_ok(const char* who, int rows, int cols)
 {
     if (rows <= jenc::kMaxDim && cols <= jenc::kMaxDim) return true;
@@ -217,6 +228,9 @@ int pf_jpeg_encode_bgr(const uint8_t* bgr, int rows, int cols, size_t step, int 
 }
 int pf_tiff_write_bgr(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double model_transform[16], int force_bigtiff)
 { return pf::write_tiff_file("pf_tiff_write_bgr", filename, bgr, rows, cols, step, quality, bg, model_transform, force_bigtiff != 0); }
+int pf_tiff_write_bgr_masked(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                             int quality, int bg, const double model_transform[16], int force_bigtiff)
+{ return pf::write_tiff_masked_file("pf_tiff_write_bgr_masked", filename, bgr, rows, cols, step, mask, mask_step, quality, bg, model_transform, force_bigtiff != 0); }
 int pf_image_info(const char* filename, int* rows, int* cols)
 {
     if (!filename || !rows || !cols) return 0;

@@ -21,6 +21,9 @@ inline bool route_on_device(SaveRoute r) { return r == SaveRoute::DeviceJpeg || 
 // PNG (zlib) / PPM / JPEG / plain TIFF by the name, as cv::imwrite picks
 bool write_image_file(const char* filename, const uint8_t* bgr, int rows, int cols);
 bool write_tiff_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff);
+// the masked file (pf_tiff_write_bgr_masked): mask is a byte per pixel, non-zero = covered, rows of mask_step bytes (0 = packed)
+bool write_tiff_masked_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                            int quality, int bg, const double* model_transform, bool force_bigtiff);
 bool jpeg_size_ok(const char* who, int rows, int cols);
 bool write_bytes_file(const char* filename, const uint8_t* data, size_t len);
 

@@ -10,7 +10,10 @@
 //   k_overview_copy  image 0 into such a buffer (only an image that is not whole tiles already: a mosaic of map tiles is used
 //                    where it lies).
 // Algorithmic bytes of the chain: 3 R C read + 3 sum_k r_k c_k written, about 1.33 x the mosaic.
+// The masked file's masks are bit planes made by coverage.hip beside the chain; their flags travel with the chain's, and only the
+// mask tiles that are neither all zero nor all one are gathered and fetched.
 #include "tiff_pyramid.hpp"
+#include "coverage.hpp"
 #include "jpeg_decode.hpp"          // set_error
 #include <hip/hip_runtime.h>
 
@@ -177,7 +180,17 @@ struct TiffDevice::Impl {
     uint8_t* land = nullptr; size_t land_cap = 0;        // page-locked: the streams of all tiles, back to back
     uint8_t* hflags = nullptr; size_t hflags_cap = 0;    // page-locked: the flags
     size_t n_tiles = 0, n_empty = 0;
-    ~Impl() { levels.release(); flags.release(); if (land) (void)hipHostFree(land); if (hflags) (void)hipHostFree(hflags); }
+    // the masked file: the masks' bit planes of all levels back to back, (offset, row step) of the tiles to gather, those tiles
+    Buf planes, where, gathered;
+    uint8_t* mland = nullptr; size_t mland_cap = 0;      // page-locked: the gathered mask tiles
+    size_t n_zero = 0, n_one = 0, own_bytes = 0;
+    ~Impl()
+    {
+        levels.release(); flags.release(); planes.release(); where.release(); gathered.release();
+        if (land) (void)hipHostFree(land);
+        if (hflags) (void)hipHostFree(hflags);
+        if (mland) (void)hipHostFree(mland);
+    }
     bool grow_land(size_t need, size_t used, size_t hint)
     {
         if (need <= land_cap) return true;
@@ -200,13 +213,27 @@ void TiffDevice::last_counts(size_t* tiles, size_t* empty, size_t* device_bytes)
     if (device_bytes) *device_bytes = p_ ? p_->levels.cap + p_->flags.cap : 0;
 }
 
+void TiffDevice::last_mask_counts(size_t* zero, size_t* one, size_t* own_bytes) const
+{
+    if (zero) *zero = p_ ? p_->n_zero : 0;
+    if (one) *one = p_ ? p_->n_one : 0;
+    if (own_bytes) *own_bytes = p_ ? p_->own_bytes : 0;
+}
+
 bool TiffDevice::write(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff,
-                       JpegEncoder& enc, void* stream)
+                       JpegEncoder& enc, void* stream, const Mask* mask)
 {
     hipStream_t s = (hipStream_t)stream;
     if (!filename || !dev_bgr || rows < 1 || cols < 1) { set_error("tiff: no name, no image or a size that is not positive"); return false; }
     if (step == 0) step = (size_t)cols * 3;
     if (step < (size_t)cols * 3) { set_error("tiff: step is smaller than a row"); return false; }
+    size_t mstep = 0;
+    if (mask) {
+        if (!mask->dev_bytes && !mask->dev_table) { set_error("tiff: no mask"); return false; }
+        mstep = mask->step ? mask->step : (size_t)cols;
+        if (mask->dev_bytes && mstep < (size_t)cols) { set_error("tiff: step is smaller than a row"); return false; }
+        if (!mask->dev_bytes && (mask->wx < 1 || mask->wy < 1 || rows != mask->wy * kTile || cols != mask->wx * kTile)) { set_error("tiff: the tile table is not the mosaic's"); return false; }
+    }
     if (!p_) p_ = new Impl();
     Impl& d = *p_;
     const std::vector<Level> lv = levels(rows, cols);
@@ -217,12 +244,19 @@ bool TiffDevice::write(const char* filename, const void* dev_bgr, int rows, int 
     std::vector<size_t> at(nl, 0), lstep(nl, 0);
     size_t bytes = 0;
     for (size_t k = in_place ? 1 : 0; k < nl; k++) { at[k] = bytes; lstep[k] = round_tile(lv[k].cols) * 3; bytes += round_tile(lv[k].rows) * lstep[k]; }
-    if (!d.levels.reserve(bytes + 16) || !d.flags.reserve(nt)) return false;
-    if (nt > d.hflags_cap) {
+    const size_t nf = mask ? 3 * nt : nt;          // flags: "all background", then for the masks "all zero" and "all one"
+    if (!d.levels.reserve(bytes + 16) || !d.flags.reserve(nf)) return false;
+    if (nf > d.hflags_cap) {
         if (d.hflags) (void)hipHostFree(d.hflags);
         d.hflags = nullptr; d.hflags_cap = 0;
-        TIFF_OK(hipHostMalloc((void**)&d.hflags, nt + 64, hipHostMallocDefault));
-        d.hflags_cap = nt + 64;
+        TIFF_OK(hipHostMalloc((void**)&d.hflags, nf + 64, hipHostMallocDefault));
+        d.hflags_cap = nf + 64;
+    }
+    std::vector<size_t> pat(nl, 0);                 // where every level's mask plane lies
+    if (mask) {
+        size_t pbytes = 0;
+        for (size_t k = 0; k < nl; k++) { pat[k] = pbytes; pbytes += coverage_plane_rows(lv[k].rows) * coverage_plane_step(lv[k].cols); }
+        if (!d.planes.reserve(pbytes)) return false;
     }
     std::vector<const uint8_t*> base(nl);
     for (size_t k = 0; k < nl; k++) base[k] = (uint8_t*)d.levels.p + at[k];
@@ -232,7 +266,14 @@ bool TiffDevice::write(const char* filename, const void* dev_bgr, int rows, int 
         hipLaunchKernelGGL(k_overview_copy, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, (const uint8_t*)dev_bgr, step, rows, cols, (uint8_t*)base[0], (int)round_tile(rows), (int)round_tile(cols));
     }
     uint8_t* flags = (uint8_t*)d.flags.p;
-    TIFF_OK(hipMemsetAsync(flags, 1, nt, s));
+    TIFF_OK(hipMemsetAsync(flags, 1, nf, s));
+    if (mask) {          // the masks' chain: level 0 from the bytes or from the map's weights, every other level from the one above
+        uint8_t* const pl = (uint8_t*)d.planes.p;
+        if (mask->dev_bytes) launch_coverage_bytes(s, (const uint8_t*)mask->dev_bytes, rows, cols, mstep, pl, flags + nt, flags + 2 * nt);
+        else launch_coverage_tiles(s, mask->dev_table, mask->wx, mask->wy, mask->w_off, pl, flags + nt, flags + 2 * nt);
+        for (size_t k = 1; k < nl; k++)
+            launch_mask_overview(s, pl + pat[k - 1], lv[k - 1].rows, lv[k - 1].cols, pl + pat[k], flags + nt + lv[k].first, flags + 2 * nt + lv[k].first);
+    }
     for (size_t k = 0; k == 0 || k + 1 < nl; k += 3) {
         OvArgs a{};
         a.src = base[k]; a.sstep = lstep[k]; a.r0 = lv[k].rows; a.c0 = lv[k].cols;
@@ -253,8 +294,45 @@ bool TiffDevice::write(const char* filename, const void* dev_bgr, int rows, int 
         if (a.nlev < 3) break;
     }
     TIFF_OK(hipGetLastError());
-    TIFF_OK(hipMemcpyAsync(d.hflags, flags, nt, hipMemcpyDeviceToHost, s));
+    TIFF_OK(hipMemcpyAsync(d.hflags, flags, nf, hipMemcpyDeviceToHost, s));
     TIFF_OK(hipStreamSynchronize(s));
+    // the mask tiles that are stored on their own are gathered and fetched behind the flags; the tile encode below runs meanwhile
+    std::vector<uint8_t> mkind;
+    std::vector<size_t> mwhere(mask ? nt : 0, 0);
+    std::vector<uint64_t> gather;
+    if (mask) {
+        mkind.assign(nt, kMaskOwn);
+        d.n_zero = d.n_one = 0;
+        for (size_t k = 0; k < nl; k++) {
+            const Level& l = lv[k];
+            const size_t pstep = coverage_plane_step(l.cols);
+            for (size_t i = 0; i < l.tiles(); i++) {
+                const size_t g = l.first + i;
+                if (d.hflags[nt + g]) { mkind[g] = kMaskZero; d.n_zero++; }
+                else if (d.hflags[2 * nt + g]) { mkind[g] = kMaskOne; d.n_one++; }
+                else {
+                    mwhere[g] = gather.size() / 2 * kMaskTileBytes;
+                    gather.push_back(pat[k] + (i / l.tx) * kTile * pstep + (i % l.tx) * (size_t)(kTile / 8));
+                    gather.push_back(pstep);
+                }
+            }
+        }
+        const size_t n_own = gather.size() / 2;
+        d.own_bytes = n_own * kMaskTileBytes;
+        if (n_own) {
+            if (!d.where.reserve(gather.size() * 8) || !d.gathered.reserve(d.own_bytes)) return false;
+            if (d.own_bytes > d.mland_cap) {
+                if (d.mland) (void)hipHostFree(d.mland);
+                d.mland = nullptr; d.mland_cap = 0;
+                TIFF_OK(hipHostMalloc((void**)&d.mland, d.own_bytes + 4096, hipHostMallocDefault));
+                d.mland_cap = d.own_bytes + 4096;
+            }
+            TIFF_OK(hipMemcpyAsync(d.where.p, gather.data(), gather.size() * 8, hipMemcpyHostToDevice, s));
+            launch_mask_gather(s, (const uint8_t*)d.planes.p, (const uint64_t*)d.where.p, (int)n_own, (uint8_t*)d.gathered.p);
+            TIFF_OK(hipGetLastError());
+            TIFF_OK(hipMemcpyAsync(d.mland, d.gathered.p, d.own_bytes, hipMemcpyDeviceToHost, s));
+        }
+    }
     // the tiles that are not empty, level by level, in batches: a tile is the window at (ty * 256) rows, (tx * 768) bytes of its level
     std::vector<uint32_t> len(nt, 0);
     std::vector<size_t> where(nt, 0), off(kBatchTiles + 1);
@@ -286,8 +364,14 @@ bool TiffDevice::write(const char* filename, const void* dev_bgr, int rows, int 
     std::vector<uint8_t> empty;
     empty_stream(quality, bg, empty);
     Layout lo;
-    layout(lv, len, (uint32_t)empty.size(), model_transform, force_bigtiff, lo);
-    return write_file(filename, lo, len, empty, [&](size_t i) { return (const uint8_t*)d.land + where[i]; });
+    if (!mask) {
+        layout(lv, len, (uint32_t)empty.size(), model_transform, force_bigtiff, lo);
+        return write_file(filename, lo, len, empty, [&](size_t i) { return (const uint8_t*)d.land + where[i]; });
+    }
+    TIFF_OK(hipStreamSynchronize(s));          // the gathered mask tiles have landed
+    layout_masked(lv, len, (uint32_t)empty.size(), &mkind, model_transform, force_bigtiff, lo);
+    const std::function<const uint8_t*(size_t)> mtile = [&](size_t i) { return (const uint8_t*)d.mland + mwhere[i]; };
+    return write_file(filename, lo, len, empty, [&](size_t i) { return (const uint8_t*)d.land + where[i]; }, &mkind, &mtile);
 }
 
 }  // namespace pf

@@ -6,6 +6,10 @@
 //
 // Header-only host code, no device: image_io.cpp (pf_tiff_write_bgr, pf_write_image), overview.hip (the same file from an image
 // in HBM), tests/cpp/san_tiff.cpp.
+//
+// The masked file (pf_tiff_write_bgr_masked) is the same file with a transparency mask behind every image: 1 bit per pixel,
+// uncompressed tiles of 256 rows x 32 bytes, image k + 1's mask the OR of the 2 x 2 blocks of image k's, all-zero and all-one
+// tiles stored once.  The same layout function places it; with no mask it places today's bytes.
 #pragma once
 #include "jpeg_encode.hpp"
 #include <cstdio>
@@ -55,7 +59,14 @@ struct Layout {
     std::vector<uint64_t> offset;       // per tile: where its stream lies (empty tiles: the shared one)
     uint64_t empty_offset = 0;          // of the shared stream (0: no tile is empty)
     uint64_t total = 0;                 // bytes of the file
+    // the masked file only
+    std::vector<uint64_t> mask_offset;  // per tile: where its mask tile lies (all-zero and all-one tiles: the shared ones)
+    uint64_t zero_offset = 0, one_offset = 0;          // of the shared mask tiles (0: no tile of that kind)
 };
+
+// a mask tile: 256 rows of 32 bytes, bit 7 of byte 0 = column 0, bits past the image 0.  Its kind decides where it is stored
+constexpr size_t kMaskTileBytes = (size_t)kTile * kTile / 8;
+enum MaskKind : uint8_t { kMaskZero = 0, kMaskOne = 1, kMaskOwn = 2 };          // all 65 536 bits 0 / all 1 (both stored once) / stored on its own
 
 namespace detail {
 struct Entry { uint16_t tag, type; uint64_t count; std::vector<uint8_t> value; };          // value: little-endian bytes
@@ -66,7 +77,9 @@ inline Entry longs(uint16_t tag, std::initializer_list<unsigned> v) { Entry e{ t
 }  // namespace detail
 
 // len[i]: bytes of tile i's stream, 0 for an empty tile; empty_len: bytes of the shared stream.  model_transform may be null.
-inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const double* model_transform, bool big, Layout& out)
+// mkind (null: the unmasked file): the MaskKind of tile i's mask tile.  Then every image's IFD is followed by its mask's, the two
+// shared mask tiles lie behind the shared stream and the other mask tiles behind the last stream, image by image, row-major.
+inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const std::vector<uint8_t>* mkind, const double* model_transform, bool big, Layout& out)
 {
     using namespace detail;
     out = Layout();
@@ -76,29 +89,32 @@ inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>&
     put(h, 0x4949, 2);
     if (big) { put(h, 43, 2); put(h, 8, 2); put(h, 0, 2); put(h, 16, 8); }
     else { put(h, 42, 2); put(h, 8, 4); }
-    struct Fix { size_t at; size_t first; size_t n; };          // where an image's TileOffsets values lie in `head`
+    struct Fix { size_t at; size_t first; size_t n; bool mask; };          // where an image's TileOffsets values lie in `head`
     std::vector<Fix> fix;
-    for (size_t k = 0; k < lv.size(); k++) {
+    const int halves = mkind ? 2 : 1;                                       // the image, then its mask
+    for (size_t k = 0; k < lv.size(); k++)
+      for (int half = 0; half < halves; half++) {
         const Level& l = lv[k];
         const size_t n = l.tiles();
+        const bool mask = half == 1;
         std::vector<Entry> e;
-        e.push_back(longs(254, { k ? 1u : 0u }));
+        e.push_back(longs(254, { (k ? 1u : 0u) | (mask ? 4u : 0u) }));
         e.push_back(longs(256, { (unsigned)l.cols }));
         e.push_back(longs(257, { (unsigned)l.rows }));
-        e.push_back(shorts(258, { 8, 8, 8 }));
-        e.push_back(shorts(259, { 7 }));
-        e.push_back(shorts(262, { 6 }));
-        e.push_back(shorts(277, { 3 }));
+        if (mask) e.push_back(shorts(258, { 1 })); else e.push_back(shorts(258, { 8, 8, 8 }));
+        e.push_back(shorts(259, { mask ? 1u : 7u }));
+        e.push_back(shorts(262, { mask ? 4u : 6u }));
+        e.push_back(shorts(277, { mask ? 1u : 3u }));
         e.push_back(shorts(284, { 1 }));
         e.push_back(shorts(322, { (unsigned)kTile }));
         e.push_back(shorts(323, { (unsigned)kTile }));
         Entry to{ 324, (uint16_t)(big ? 16 : 4), n, std::vector<uint8_t>(n * osz, 0) };          // filled in below
         e.push_back(to);
         Entry tb{ 325, 4, n, {} };
-        for (size_t i = 0; i < n; i++) put(tb.value, len[l.first + i] ? len[l.first + i] : empty_len, 4);
+        for (size_t i = 0; i < n; i++) put(tb.value, mask ? (uint32_t)kMaskTileBytes : len[l.first + i] ? len[l.first + i] : empty_len, 4);
         e.push_back(tb);
-        e.push_back(shorts(530, { 2, 2 }));
-        if (k == 0 && model_transform) {
+        if (!mask) e.push_back(shorts(530, { 2, 2 }));
+        if (k == 0 && !mask && model_transform) {
             Entry mt{ 34264, 12, 16, {} };
             for (int i = 0; i < 16; i++) { uint64_t bits; std::memcpy(&bits, &model_transform[i], 8); put(mt.value, bits, 8); }
             e.push_back(mt);
@@ -113,21 +129,21 @@ inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>&
         for (const Entry& en : e) {
             put(h, en.tag, 2); put(h, en.type, 2); put(h, en.count, osz);
             if ((int)en.value.size() <= osz) {
-                if (en.tag == 324) fix.push_back({ h.size(), l.first, n });
+                if (en.tag == 324) fix.push_back({ h.size(), l.first, n, mask });
                 h.insert(h.end(), en.value.begin(), en.value.end());
                 h.resize(h.size() + (osz - en.value.size()), 0);
             } else {
-                if (en.tag == 324) fix.push_back({ values + tail.size(), l.first, n });
+                if (en.tag == 324) fix.push_back({ values + tail.size(), l.first, n, mask });
                 put(h, values + tail.size(), osz);
                 tail.insert(tail.end(), en.value.begin(), en.value.end());
                 if (tail.size() & 1) tail.push_back(0);
             }
         }
         const size_t next = values + tail.size();
-        put(h, k + 1 < lv.size() ? next : 0, osz);
+        put(h, k + 1 < lv.size() || half + 1 < halves ? next : 0, osz);
         h.resize(values, 0);
         h.insert(h.end(), tail.begin(), tail.end());
-    }
+      }
     // the streams
     const size_t nt = tile_count(lv);
     out.offset.assign(nt, 0);
@@ -135,21 +151,37 @@ inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>&
     bool any_empty = false;
     for (size_t i = 0; i < nt; i++) any_empty = any_empty || !len[i];
     if (any_empty) { out.empty_offset = at; at += empty_len; at += at & 1; }
+    if (mkind) {          // the shared mask tiles (8192 bytes each: the offsets stay even)
+        bool any_zero = false, any_one = false;
+        for (size_t i = 0; i < nt; i++) { any_zero = any_zero || (*mkind)[i] == kMaskZero; any_one = any_one || (*mkind)[i] == kMaskOne; }
+        if (any_zero) { out.zero_offset = at; at += kMaskTileBytes; }
+        if (any_one) { out.one_offset = at; at += kMaskTileBytes; }
+    }
     for (size_t i = 0; i < nt; i++) {
         if (!len[i]) { out.offset[i] = out.empty_offset; continue; }
         out.offset[i] = at; at += len[i]; at += at & 1;
     }
+    if (mkind) {
+        out.mask_offset.assign(nt, 0);
+        for (size_t i = 0; i < nt; i++) {
+            if ((*mkind)[i] == kMaskZero) out.mask_offset[i] = out.zero_offset;
+            else if ((*mkind)[i] == kMaskOne) out.mask_offset[i] = out.one_offset;
+            else { out.mask_offset[i] = at; at += kMaskTileBytes; }
+        }
+    }
     out.total = at;
     if (!big && at > 0xFFFFFFFFull) return false;
     for (const Fix& f : fix)
-        for (size_t i = 0; i < f.n; i++) poke(h, f.at + i * osz, out.offset[f.first + i], osz);
+        for (size_t i = 0; i < f.n; i++) poke(h, f.at + i * osz, f.mask ? out.mask_offset[f.first + i] : out.offset[f.first + i], osz);
     return true;
 }
 
-inline void layout(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const double* model_transform, bool force_bigtiff, Layout& out)
+inline void layout_masked(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const std::vector<uint8_t>* mkind, const double* model_transform, bool force_bigtiff, Layout& out)
 {
-    if (force_bigtiff || !layout_as(lv, len, empty_len, model_transform, false, out)) (void)layout_as(lv, len, empty_len, model_transform, true, out);
+    if (force_bigtiff || !layout_as(lv, len, empty_len, mkind, model_transform, false, out)) (void)layout_as(lv, len, empty_len, mkind, model_transform, true, out);
 }
+inline void layout(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const double* model_transform, bool force_bigtiff, Layout& out)
+{ layout_masked(lv, len, empty_len, nullptr, model_transform, force_bigtiff, out); }
 
 // the stream every empty tile points at: 256 x 256 pixels of the background colour
 inline void empty_stream(int quality, int bg, std::vector<uint8_t>& out)
@@ -160,9 +192,12 @@ inline void empty_stream(int quality, int bg, std::vector<uint8_t>& out)
 }
 
 // The file: the head, then the streams where the layout put them.  stream(i): the bytes of tile i (len[i] of them, len[i] > 0),
-// asked for in increasing i.  A file that cannot be written completely is removed.
+// asked for in increasing i.  The masked file (mkind and mtile given): the two shared mask tiles behind the shared stream, and
+// behind the last stream mtile(i), the 8192 bytes of every mask tile of kind kMaskOwn, in increasing i.  A file that cannot be
+// written completely is removed.
 inline bool write_file(const char* filename, const Layout& lo, const std::vector<uint32_t>& len, const std::vector<uint8_t>& empty,
-                       const std::function<const uint8_t*(size_t)>& stream)
+                       const std::function<const uint8_t*(size_t)>& stream, const std::vector<uint8_t>* mkind = nullptr,
+                       const std::function<const uint8_t*(size_t)>* mtile = nullptr)
 {
     FILE* f = std::fopen(filename, "wb");
     if (!f) { set_error(std::string("save: cannot open ") + filename); return false; }
@@ -171,8 +206,16 @@ inline bool write_file(const char* filename, const Layout& lo, const std::vector
     auto even = [&]() { const uint8_t z = 0; return !(at & 1) || put(&z, 1); };
     bool ok = put(lo.head.data(), lo.head.size());
     if (ok && lo.empty_offset) ok = put(empty.data(), empty.size()) && even();
+    if (ok && mkind) {
+        const std::vector<uint8_t> zero(kMaskTileBytes, 0), one(kMaskTileBytes, 0xFF);
+        if (lo.zero_offset) ok = at == lo.zero_offset && put(zero.data(), zero.size());
+        if (ok && lo.one_offset) ok = at == lo.one_offset && put(one.data(), one.size());
+    }
     for (size_t i = 0; ok && i < len.size(); i++)
         if (len[i]) ok = at == lo.offset[i] && put(stream(i), len[i]) && even();
+    if (mkind)
+        for (size_t i = 0; ok && i < mkind->size(); i++)
+            if ((*mkind)[i] == kMaskOwn) ok = at == lo.mask_offset[i] && put((*mtile)(i), kMaskTileBytes);
     ok = ok && at == lo.total;
     if (std::fclose(f) != 0) ok = false;
     if (!ok) { std::remove(filename); set_error("save: write failed"); }
@@ -211,8 +254,39 @@ inline bool cut_tile(const uint8_t* img, int rows, int cols, size_t step, int ty
     return empty;
 }
 
-// pf_tiff_write_bgr
-inline bool write_bgr(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff)
+// the coverage of image k + 1 from that of image k (a byte per pixel, 0 or 1, packed rows): the OR of the 2 x 2 block, a missing
+// last row or column repeats the one before it
+inline void mask_halve(const uint8_t* src, int rows, int cols, std::vector<uint8_t>& dst)
+{
+    const int r2 = (rows + 1) / 2, c2 = (cols + 1) / 2;
+    dst.resize((size_t)r2 * c2);
+    for (int y = 0; y < r2; y++) {
+        const uint8_t* a = src + (size_t)(2 * y) * cols;
+        const uint8_t* b = src + (size_t)std::min(2 * y + 1, rows - 1) * cols;
+        for (int x = 0; x < c2; x++) {
+            const int x1 = std::min(2 * x + 1, cols - 1);
+            dst[(size_t)y * c2 + x] = (uint8_t)(a[2 * x] | a[x1] | b[2 * x] | b[x1]);
+        }
+    }
+}
+// mask tile (ty, tx) of such a coverage: 256 rows of 32 bytes, bit 7 of byte 0 = column 0, bits past the image 0; returns its kind
+inline MaskKind cut_mask_tile(const uint8_t* cov, int rows, int cols, int ty, int tx, uint8_t* tile)
+{
+    std::memset(tile, 0, kMaskTileBytes);
+    size_t ones = 0;
+    const int x0 = tx * kTile, n = std::min(kTile, cols - x0);
+    for (int r = 0; r < kTile && ty * kTile + r < rows; r++) {
+        const uint8_t* s = cov + (size_t)(ty * kTile + r) * cols + x0;
+        uint8_t* d = tile + (size_t)r * (kTile / 8);
+        for (int x = 0; x < n; x++)
+            if (s[x]) { d[x >> 3] |= (uint8_t)(0x80 >> (x & 7)); ones++; }
+    }
+    return ones == 0 ? kMaskZero : ones == (size_t)kTile * kTile ? kMaskOne : kMaskOwn;
+}
+
+// pf_tiff_write_bgr (mask == null) and pf_tiff_write_bgr_masked (mask: a byte per pixel, non-zero = covered, rows of mask_step bytes)
+inline bool write_pyramid(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                          int quality, int bg, const double* model_transform, bool force_bigtiff)
 {
     const std::vector<Level> lv = levels(rows, cols);
     const uint8_t bgv = background_byte(bg);
@@ -234,9 +308,36 @@ inline bool write_bgr(const char* filename, const uint8_t* bgr, int rows, int co
     }
     empty_stream(quality, bg, empty);
     Layout lo;
-    layout(lv, len, (uint32_t)empty.size(), model_transform, force_bigtiff, lo);
-    return write_file(filename, lo, len, empty, [&](size_t i) { return streams.data() + at[i]; });
+    if (!mask) {
+        layout(lv, len, (uint32_t)empty.size(), model_transform, force_bigtiff, lo);
+        return write_file(filename, lo, len, empty, [&](size_t i) { return streams.data() + at[i]; });
+    }
+    // the masks: the OR chain, every tile packed and classed; the tiles that are stored on their own are kept back to back
+    std::vector<uint8_t> mkind(len.size(), kMaskZero), mtiles, cov((size_t)rows * cols), cnext;
+    std::vector<size_t> mat(len.size(), 0);
+    for (int y = 0; y < rows; y++)
+        for (int x = 0; x < cols; x++) cov[(size_t)y * cols + x] = mask[(size_t)y * mask_step + x] ? 1 : 0;
+    for (size_t k = 0; k < lv.size(); k++) {
+        const Level& l = lv[k];
+        if (k) { mask_halve(cov.data(), lv[k - 1].rows, lv[k - 1].cols, cnext); cov.swap(cnext); }
+        for (int ty = 0; ty < l.ty; ty++)
+            for (int tx = 0; tx < l.tx; tx++) {
+                const size_t i = l.first + (size_t)ty * l.tx + tx;
+                mat[i] = mtiles.size();
+                mtiles.resize(mtiles.size() + kMaskTileBytes);
+                mkind[i] = cut_mask_tile(cov.data(), l.rows, l.cols, ty, tx, mtiles.data() + mat[i]);
+                if (mkind[i] != kMaskOwn) mtiles.resize(mat[i]);
+            }
+    }
+    layout_masked(lv, len, (uint32_t)empty.size(), &mkind, model_transform, force_bigtiff, lo);
+    const std::function<const uint8_t*(size_t)> mtile = [&](size_t i) { return (const uint8_t*)mtiles.data() + mat[i]; };
+    return write_file(filename, lo, len, empty, [&](size_t i) { return streams.data() + at[i]; }, &mkind, &mtile);
 }
+inline bool write_bgr(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff)
+{ return write_pyramid(filename, bgr, rows, cols, step, nullptr, 0, quality, bg, model_transform, force_bigtiff); }
+inline bool write_bgr_masked(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                             int quality, int bg, const double* model_transform, bool force_bigtiff)
+{ return write_pyramid(filename, bgr, rows, cols, step, mask, mask_step, quality, bg, model_transform, force_bigtiff); }
 
 }  // namespace tiff
 
@@ -250,10 +351,18 @@ public:
     void release();          // frees the device and page-locked buffers (the device they live on is current)
     TiffDevice(const TiffDevice&) = delete;
     TiffDevice& operator=(const TiffDevice&) = delete;
+    // The masked file's coverage, if any: a byte per pixel in device memory (non-zero = covered, rows of `step` bytes), or the tile
+    // table of a map's mosaic (wx x wy slots of 256 x 256, 0 = no tile; covered = the fp32 weight at w_off inside the slot is not 0).
+    struct Mask {
+        const void* dev_bytes = nullptr; size_t step = 0;
+        const uint64_t* dev_table = nullptr; int wx = 0, wy = 0; uint32_t w_off = 0;
+    };
     bool write(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff,
-               JpegEncoder& enc, void* stream);
+               JpegEncoder& enc, void* stream, const Mask* mask = nullptr);
     // diagnostics of the last write: tiles of all images, the empty ones among them, bytes of device memory held for levels and flags
     void last_counts(size_t* tiles, size_t* empty, size_t* device_bytes) const;
+    // ... of the last masked write: mask tiles that are all zero, all one, and the bytes of the others (what crossed to the host)
+    void last_mask_counts(size_t* zero, size_t* one, size_t* own_bytes) const;
 private:
     struct Impl;
     Impl* p_ = nullptr;

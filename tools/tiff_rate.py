@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """save("m.tif") on the bench mosaic (dev tool; the mosaic is tools/blend_save_rate.py's): wall time of save(".tif"), save(".jpg") and of
 writing a file of the .tif's size alone, on the same map in the same process, interleaved, median of --reps after a warm-up round.
-usage: tools/tiff_rate.py [--int16] [--frames N] [--reps R] [--dir D] [--kernels-only] [--no-check]
+usage: tools/tiff_rate.py [--int16] [--frames N] [--reps R] [--dir D] [--kernels-only] [--no-check] [--masked]
+  --masked         save_tiff_masked beside save_tiff on the same map, interleaved: wall times (median, min, max, every run), the mask tiles
+                   of the file by kind, the mask bytes that crossed to the host, the file's size against the unmasked file's, and the file
+                   against the host writer once (pf_tiff_write_bgr_masked).  With --kernels-only: a few masked saves for the profiler
+                   (k_coverage_tiles, k_mask_overview, k_mask_gather).
   --kernels-only   a few save(".tif") and save(".jpg") and nothing else: the run to put under
                    rocprofv3 --kernel-trace --stats -d OUT -- python tools/tiff_rate.py --kernels-only
                    (k_overview*, the k_jenc_* kernels of the tile encode and of the whole-image encode; wall times under the profiler mean nothing)
@@ -13,7 +17,7 @@ sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import bench
 ap = argparse.ArgumentParser(); ap.add_argument("--int16", action="store_true"); ap.add_argument("--frames", type=int, default=120)
 ap.add_argument("--reps", type=int, default=5); ap.add_argument("--dir", default=None); ap.add_argument("--kernels-only", action="store_true")
-ap.add_argument("--no-check", action="store_true")
+ap.add_argument("--no-check", action="store_true"); ap.add_argument("--masked", action="store_true")
 a = ap.parse_args()
 import numpy as np, torch
 pf = bench.load_package(); wl = importlib.import_module("pi_slam_fusion_amd.workloads")
@@ -31,6 +35,48 @@ def used_mb():
 with tempfile.TemporaryDirectory(dir=a.dir) as d:
     tif, jpg, raw = os.path.join(d, "m.tif"), os.path.join(d, "m.jpg"), os.path.join(d, "m.bin")
     base = used_mb()
+    if a.kernels_only and a.masked:
+        for _ in range(3):
+            assert m.save_tiff_masked(tif)
+        print("kernels-only: 3 x save_tiff_masked, file %d bytes" % os.path.getsize(tif))
+        sys.exit(0)
+    if a.masked:
+        mt = os.path.join(d, "masked.tif")
+        def t_plain():
+            t0 = time.perf_counter(); assert m.save_tiff(tif); return time.perf_counter() - t0
+        def t_masked():
+            t0 = time.perf_counter(); assert m.save_tiff_masked(mt); return time.perf_counter() - t0
+        t_plain(); t_masked()                                     # warm-up: code objects, buffers, page-locked memory
+        times = {"plain": [], "masked": []}
+        for _ in range(max(a.reps, 5)):
+            times["plain"].append(t_plain()); times["masked"].append(t_masked())
+        import tiff_model as tm, tiff_mask_model as mm
+        data = open(mt, "rb").read()
+        big, ifds = tm.parse(data)
+        kinds = {"zero": 0, "one": 0, "own": 0}
+        for i in ifds[1::2]:
+            for o in i["tags"][324][1]:
+                kinds[mm.kind_of(data[o:o + mm.TILE_BYTES])] += 1
+        nt = sum(kinds.values())
+        rows, cols = ifds[0]["tags"][257][1][0], ifds[0]["tags"][256][1][0]
+        print("mosaic %d x %d (%d map tiles), %d images + %d masks, %d reps interleaved:" % (cols, rows, len(m.tiles()), len(ifds) // 2, len(ifds) // 2, len(times["plain"])))
+        for k, label in (("plain", "save_tiff(m.tif)"), ("masked", "save_tiff_masked(m.tif)")):
+            v = times[k]
+            print("  %-26s median %8.1f ms  (min %.1f, max %.1f; runs %s)" % (label, statistics.median(v) * 1e3, min(v) * 1e3, max(v) * 1e3, " ".join("%.1f" % (x * 1e3) for x in v)))
+        print("  masked - plain, medians: %+.1f ms" % ((statistics.median(times["masked"]) - statistics.median(times["plain"])) * 1e3))
+        print("  mask tiles %d: %d all zero, %d all one (each kind stored once), %d stored on their own" % (nt, kinds["zero"], kinds["one"], kinds["own"]))
+        print("  mask bytes that crossed to the host: %d of tiles + %d of flags (the unmasked save: %d of flags); level-0 plane %d bytes stays in HBM" %
+              (kinds["own"] * mm.TILE_BYTES, 3 * nt, nt, rows * cols // 8))
+        print("  file %d bytes masked, %d unmasked: %+d (%.3f %%)" % (len(data), os.path.getsize(tif), len(data) - os.path.getsize(tif), 100.0 * (len(data) - os.path.getsize(tif)) / os.path.getsize(tif)))
+        if not a.no_check:
+            mem, mask, org = m.save_to_memory_mask()
+            dims, geo = m.grid()
+            xf = [geo[5], 0, 0, geo[0] + (org[0] - dims[2]) * geo[4], 0, geo[5], 0, geo[1] + (org[1] - dims[3]) * geo[4], 0, 0, 1, 0, 0, 0, 0, 1]
+            assert pf.tiff_write_masked(raw, mem, mask, 95, 0, xf)
+            ok = open(raw, "rb").read() == data
+            print("  file == pf_tiff_write_bgr_masked(save_to_memory_mask, 95, 0, transform, 0): %s;  covered %.1f %% of the bounding box" % (ok, 100.0 * (mask != 0).mean()))
+            assert ok
+        sys.exit(0)
     if a.kernels_only:
         for _ in range(3):
             assert m.save(tif) and m.save(jpg)
