@@ -276,8 +276,24 @@ int     pf_blend_tiles(pf_map* m, const int* xy, int n, uint8_t* bgr);
  * encode pass per blend launch covers all its tiles.  A tile without pyramid gives an empty range.  0 + pf_last_error() when the
  * streams do not fit `cap` (pf_jpeg_encode_bgr's bound for 256 x 256, times n, always fits). */
 int     pf_blend_tiles_jpeg(pf_map* m, const int* xy, int n, int quality, uint8_t* out, size_t cap, size_t* offsets);
+/* --- reduced-resolution views: the pyramid collapsed from the top and stopped at level k -------------------------------
+ * L = pf_num_levels - 1, E = 256 >> k, 0 <= k <= L.  The blended Gaussian level k: a low-passed 1 / 2^k view with the same seam
+ * blending, made from 4^-k of the tile bytes.  It is Ele::blend / save() of a map whose tiles are E pixels wide with levels
+ * k .. L: the halo of level i stays 1 << (L - i), the crop is [1 << (L - k), +E), and the mask (0 in a tile, the background
+ * colour in the mosaic) comes from the LEVEL-k weights.  k = L is the masked top level.  k = 0 is pf_blend_tiles /
+ * pf_blend_tile_raw / pf_blend_changed / pf_save_to_memory, byte for byte.  Each returns 0 with the reason in pf_last_error() and
+ * touches no output for k < 0, k > L, k > 0 on a TypeCPU / TypeGPU map (no pyramid) and k > 0 on a sharded map (shard_count > 1).
+ *
+ * pf_blend_tiles at level k: bgr n x E x E x 3 bytes and / or raw n x E x E x 3 of the pyramid type (pf_pyramid_type; a TypeCPU /
+ * TypeGPU map at level 0: four bytes a pixel, pf_get_tile_bgra's); either may be NULL.  A tile without pyramid leaves its range
+ * untouched, Ischanged is left alone.                                                                                      */
+int     pf_blend_tiles_level(pf_map* m, const int* xy, int n, int level, uint8_t* bgr, void* raw);
+/* pf_blend_changed at level k: the same tiles, the same flag clearing and return value; bgr sized by cap x E x E x 3.     */
+int     pf_blend_changed_level(pf_map* m, int level, int* xy, uint8_t* bgr, int cap);
+/* pf_save_to_memory at level k, the same two calls: rows = tiles_y * E, cols = tiles_x * E, the same origin tile.          */
+int     pf_save_to_memory_level(pf_map* m, int level, uint8_t* bgr, int* rows, int* cols, int* tile_x0, int* tile_y0);
 /* Page-locked host memory for the output side: results written into such a buffer (pf_blend_changed, pf_blend_tiles,
- * pf_save_to_memory) are copied from HBM straight into it; any other buffer is filled through the library's own pinned
+ * pf_save_to_memory and their _level forms) are copied from HBM straight into it; any other buffer is filled through the library's own pinned
  * staging ring and a host copy (the counterpart of cv::Mat's allocator for the textures updateTexture hands to GL).       */
 void*   pf_host_alloc(size_t bytes);
 void    pf_host_free(void* p);

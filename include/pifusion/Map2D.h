@@ -131,13 +131,19 @@ public:
     // tile that is not on the rim of the grid (MultiBandMap2DCPU.cpp:744-757): "Map2DUpdate LastTexMat <gpsTL> <gpsBR>".
     void draw(const std::function<void(int, int, const unsigned char*)>& sink = nullptr,
               const std::function<void(const std::string&)>& announce = nullptr)
+    { drawLevel(0, sink, announce); }
+    // draw() for a viewer that is zoomed out: the same tiles as views of pyramid level `level` (pf_blend_changed_level), BGR8
+    // E x E with E = ELE_PIXELS >> level -- the GPU minifies, and 4^-level of the pixels cross to the host
+    void drawLevel(int level, const std::function<void(int, int, const unsigned char*)>& sink = nullptr,
+                   const std::function<void(const std::string&)>& announce = nullptr)
     {
         const int cap = pf_tile_count(h_);
-        if (cap <= 0) return;
+        if (cap <= 0 || level < 0 || level > 8) return;
         std::vector<int> xy(2 * (size_t)cap);
         // the tiles come back in ONE launch and one PCIe transfer into a page-locked buffer that this object keeps between draws
         // (pf_host_alloc: filled straight from HBM; the textures updateTexture hands to GL, .cpp:159-176)
-        const size_t need = (size_t)cap * ELE_PIXELS * ELE_PIXELS * 3;
+        const size_t tile = (size_t)(ELE_PIXELS >> level) * (ELE_PIXELS >> level) * 3;
+        const size_t need = (size_t)cap * tile;
         if (tex_cap_ < need) {
             pf_host_free(tex_); tex_cap_ = 0;
             tex_ = (unsigned char*)pf_host_alloc(need + need / 4);
@@ -145,9 +151,9 @@ public:
             tex_cap_ = need + need / 4;
         }
         unsigned char* px = tex_;
-        const int n = pf_blend_changed(h_, xy.data(), px, cap);
+        const int n = level ? pf_blend_changed_level(h_, level, xy.data(), px, cap) : pf_blend_changed(h_, xy.data(), px, cap);
         for (int i = 0; i < n; i++) {
-            if (sink) sink(xy[2 * i], xy[2 * i + 1], px + (size_t)i * ELE_PIXELS * ELE_PIXELS * 3);
+            if (sink) sink(xy[2 * i], xy[2 * i + 1], px + (size_t)i * tile);
             char cmd[256];
             if (fuse2google_ && announce && pf_map_update_command(h_, xy[2 * i], xy[2 * i + 1], gps_origin_, cmd, (int)sizeof cmd) > 0) announce(cmd);
         }
@@ -175,6 +181,20 @@ public:
         return true;
     }
     bool blend(int ix, int iy, unsigned char* bgr256) { return pf_blend_tile(h_, ix, iy, bgr256) != 0; }
+    // ... as the view of pyramid level `level`: BGR8 E x E, E = ELE_PIXELS >> level (pf_blend_tiles_level).  A tile without pyramid
+    // leaves bgr untouched; false where the map has no such level
+    bool blendLevel(int ix, int iy, int level, unsigned char* bgr)
+    {
+        const int xy[2] = { ix, iy };
+        return pf_blend_tiles_level(h_, xy, 1, level, bgr, nullptr) != 0;
+    }
+    // save() without the file, at pyramid level `level` (0: the full mosaic): rows x cols x 3 BGR8 into `bgr`, the origin tile
+    bool saveToMemory(std::vector<unsigned char>& bgr, int& rows, int& cols, int& tile_x0, int& tile_y0, int level = 0)
+    {
+        if (!pf_save_to_memory_level(h_, level, nullptr, &rows, &cols, &tile_x0, &tile_y0)) return false;
+        bgr.resize((size_t)rows * cols * 3);
+        return pf_save_to_memory_level(h_, level, bgr.data(), &rows, &cols, &tile_x0, &tile_y0) != 0;
+    }
     pf_map* handle() { return h_; }
 
 private:

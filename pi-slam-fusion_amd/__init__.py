@@ -133,6 +133,10 @@ def lib():
         L.pf_blend_tiles.argtypes = [vp, ip, C.c_int, vp]
         L.pf_host_alloc.argtypes = [C.c_size_t]; L.pf_host_alloc.restype = vp
         L.pf_host_free.argtypes = [vp]; L.pf_host_free.restype = None
+    if hasattr(L, "pf_blend_tiles_level") or not os.environ.get("PF_LIB"):
+        L.pf_blend_tiles_level.argtypes = [vp, ip, C.c_int, C.c_int, vp, vp]
+        L.pf_blend_changed_level.argtypes = [vp, C.c_int, ip, vp, C.c_int]
+        L.pf_save_to_memory_level.argtypes = [vp, C.c_int, vp, ip, ip, ip, ip]
     L.pf_format_map_update.argtypes = [dp, dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_int]
     L.pf_map_update_command.argtypes = [vp, C.c_int, C.c_int, dp, C.c_char_p, C.c_int]
     L.pf_lnglat_from_distance.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, dp, dp]; L.pf_lnglat_from_distance.restype = None
@@ -507,13 +511,21 @@ class Map2D:
             if (r.value, c.value) == want:
                 return out, mask, (x0.value, y0.value)
 
-    def save_to_memory(self, alloc=None):
-        """(mosaic BGR8, (tile x0, tile y0)); alloc(shape) -> uint8 array supplies the buffer (e.g. host_array)."""
+    def save_to_memory(self, alloc=None, level=0):
+        """(mosaic BGR8, (tile x0, tile y0)); alloc(shape) -> uint8 array supplies the buffer (e.g. host_array).  level=k: the
+        mosaic collapsed down to pyramid level k, (256 >> k) pixels a tile (pf_save_to_memory_level); None where the map has no
+        such view."""
         r, c, x0, y0 = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        if not lib().pf_save_to_memory(self._h, None, C.byref(r), C.byref(c), C.byref(x0), C.byref(y0)):
+        if hasattr(lib(), "pf_save_to_memory_level"):          # (PF_LIB = an older build: level 0 through its own entry point)
+            call = lambda p: lib().pf_save_to_memory_level(self._h, level, p, C.byref(r), C.byref(c), C.byref(x0), C.byref(y0))
+        elif level == 0:
+            call = lambda p: lib().pf_save_to_memory(self._h, p, C.byref(r), C.byref(c), C.byref(x0), C.byref(y0))
+        else:
+            raise RuntimeError("this build of the library has no level views")
+        if not call(None):
             return None
         out = alloc((r.value, c.value, 3)) if alloc else np.empty((r.value, c.value, 3), np.uint8)
-        if not lib().pf_save_to_memory(self._h, out.ctypes.data, C.byref(r), C.byref(c), C.byref(x0), C.byref(y0)):
+        if not call(out.ctypes.data):
             return None
         return out, (x0.value, y0.value)
 
@@ -564,22 +576,47 @@ class Map2D:
         n = lib().pf_map_update_command(self._h, ix, iy, g, buf, 256)
         return buf.value.decode() if n > 0 else None
 
-    def blend_changed(self, cap=4096, out=None):
-        """draw()'s texture refresh: ([(ix, iy)...], n x 256 x 256 x 3 uint8).  out: a caller-owned buffer of at least cap tiles
-        (e.g. host_array(): page-locked, filled straight from HBM)."""
+    def blend_changed(self, cap=4096, out=None, level=0):
+        """draw()'s texture refresh: ([(ix, iy)...], n x E x E x 3 uint8), E = 256 >> level (level=k: the tiles as views of pyramid
+        level k, pf_blend_changed_level).  out: a caller-owned buffer of at least cap tiles (e.g. host_array(): page-locked, filled
+        straight from HBM)."""
+        e = ELE_PIXELS >> level if 0 <= level <= 8 else 1          # (a level the map refuses: nothing is written)
         xy = (C.c_int * (2 * cap))()
         if out is None:
-            out = np.empty((cap, ELE_PIXELS, ELE_PIXELS, 3), np.uint8)
-        n = lib().pf_blend_changed(self._h, xy, out.ctypes.data, cap)
+            out = np.empty((cap, e, e, 3), np.uint8)
+        if hasattr(lib(), "pf_blend_changed_level"):
+            n = lib().pf_blend_changed_level(self._h, level, xy, out.ctypes.data, cap)
+        elif level == 0:
+            n = lib().pf_blend_changed(self._h, xy, out.ctypes.data, cap)
+        else:
+            raise RuntimeError("this build of the library has no level views")
         return [(xy[2 * i], xy[2 * i + 1]) for i in range(n)], out[:n]
 
-    def blend_tiles(self, tiles, out=None):
-        """Ele::blend + 8U view of the listed tiles (Ischanged untouched); tiles without pyramid keep out's bytes."""
+    def blend_tiles(self, tiles, out=None, level=0):
+        """Ele::blend + 8U view of the listed tiles (Ischanged untouched); tiles without pyramid keep out's bytes.  level=k: the views
+        of pyramid level k, n x E x E x 3 with E = 256 >> k (pf_blend_tiles_level); None where the map has no such view."""
         n = len(tiles)
+        e = ELE_PIXELS >> level if 0 <= level <= 8 else 1
         xy = (C.c_int * (2 * n))(*[v for t in tiles for v in t])
         if out is None:
-            out = np.zeros((n, ELE_PIXELS, ELE_PIXELS, 3), np.uint8)
-        return out[:n] if lib().pf_blend_tiles(self._h, xy, n, out.ctypes.data) else None
+            out = np.zeros((n, e, e, 3), np.uint8)
+        if hasattr(lib(), "pf_blend_tiles_level"):
+            ok = lib().pf_blend_tiles_level(self._h, xy, n, level, out.ctypes.data, None)
+        elif level == 0:
+            ok = lib().pf_blend_tiles(self._h, xy, n, out.ctypes.data)
+        else:
+            raise RuntimeError("this build of the library has no level views")
+        return out[:n] if ok else None
+
+    def blend_tiles_raw(self, tiles, level=0, out=None):
+        """Ele::blend of the listed tiles in the pyramid type, before the 8U view: n x E x E x 3 of self.dtype, E = 256 >> level
+        (a TypeCPU / TypeGPU map, level 0 only: n x 256 x 256 x 4 uint8, tile_bgra's).  Tiles without pyramid keep out's bytes."""
+        n = len(tiles)
+        e = ELE_PIXELS >> level if 0 <= level <= 8 else 1
+        xy = (C.c_int * (2 * n))(*[v for t in tiles for v in t])
+        if out is None:
+            out = np.zeros((n, e, e, 4), np.uint8) if lib().pf_pyramid_type(self._h) == PF_8UC4 else np.zeros((n, e, e, 3), self.dtype)
+        return out[:n] if lib().pf_blend_tiles_level(self._h, xy, n, level, None, out.ctypes.data) else None
 
     def blend_tiles_jpeg(self, tiles, quality=95, cap=None):
         """blend_tiles whose results leave as JPEG streams (256 x 256 each, encoded on the GPU from where the blend left them):

@@ -259,6 +259,16 @@ int pf_blend_tiles(pf_map* m, const int* xy, int n, uint8_t* bgr)
     for (int i = 0; i < n; i++) tiles[i] = { xy[2 * i], xy[2 * i + 1] };
     return m->impl.blend_list(tiles, bgr);
 }
+int pf_blend_tiles_level(pf_map* m, const int* xy, int n, int level, uint8_t* bgr, void* raw)
+{
+    if (!m || !xy || (!bgr && !raw) || n <= 0) return 0;
+    std::vector<std::pair<int, int>> tiles(n);
+    for (int i = 0; i < n; i++) tiles[i] = { xy[2 * i], xy[2 * i + 1] };
+    return m->impl.blend_list_level(tiles, level, bgr, raw);
+}
+int pf_blend_changed_level(pf_map* m, int level, int* xy, uint8_t* bgr, int cap) { return (m && xy && bgr && cap > 0) ? m->impl.blend_changed(xy, bgr, cap, level) : 0; }
+int pf_save_to_memory_level(pf_map* m, int level, uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
+{ return m && rows && cols && tx0 && ty0 && m->impl.save_to_memory_level(level, bgr, rows, cols, tx0, ty0); }
 int pf_blend_tiles_jpeg(pf_map* m, const int* xy, int n, int quality, uint8_t* out, size_t cap, size_t* offsets)
 {
     if (!m || !xy || !out || !offsets || n <= 0) { pf::set_error("pf_blend_tiles_jpeg: no map, no tiles or no buffer"); return 0; }

@@ -1621,29 +1621,31 @@ bool FusionMap::download(const std::vector<OutPiece>& pieces)
 // Ele::blend (.cpp:77-146) for a list of tiles.  halo9 (nullptr, or 9 device pointers per tile) substitutes packed strip
 // sets for neighbours held by other shards.  Results land in tile order (a tile that does not exist leaves the caller's
 // bytes alone).  One launch of the fused collapse kernel per kBlendLaunch tiles, "blend with neighbours" and "blend by self"
-// tiles side by side in it; the pixels come back through download().
-bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg)
+// tiles side by side in it; the pixels come back through download().  level > 0: the view of that pyramid level (collapse_level.hip),
+// E x E pixels a tile with E = 256 >> level; no halo strips and no JPEG streams there.
+bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg, int level)
 {
     Section sec(this, T_UPDATE_TEXTURE);
+    if (level > 0 && (halo9 || jpeg)) { set_error("blend: halo strips and JPEG streams exist at level 0 only"); return false; }
 #if PF_EXPERIMENTS
     static const bool per_level = exp_env("PF_BLEND_PER_LEVEL") != nullptr;
-    if (per_level && !jpeg) return blend_batch_per_level(tiles, halo9, raw_host, bgr_host);
+    if (per_level && !jpeg && level == 0) return blend_batch_per_level(tiles, halo9, raw_host, bgr_host);
 #endif
     const bool want_bgr = bgr_host || jpeg;
     if (jpeg) { jpeg->used = 0; jpeg->offsets[0] = 0; }
     const int nl = band_num_ + 1;
     const size_t es = lay_.f32 ? 4 : 2, px = 3 * es;
-    const size_t tile_px = (size_t)kElePixels * kElePixels;
+    const size_t tile_px = (size_t)(kElePixels >> level) * (kElePixels >> level);
     if (!settle()) return false;                  // the upper levels of the last frames are still pending: run them first (stream order)
-    // algorithmic bytes of one blended tile: its own Laplacians and level-0 weights read, the result written, plus the ring of
-    // neighbour pixels the crop depends on at levels >= 1 (pyrUp reaches one pixel per level: collapse_fused.hip)
+    // algorithmic bytes of one blended tile: its own Laplacians and the weights of the result's level read, the result written, plus
+    // the ring of neighbour pixels the crop depends on at the levels above (pyrUp reaches one pixel per level: collapse_fused.hip)
     double tile_bytes[2] = { 0, 0 };
     for (int nb = 0; nb < 2; nb++) {
         double b = (double)tile_px * 4 + (raw_host ? (double)tile_px * px : 0) + (want_bgr ? (double)tile_px * 3 : 0);
-        int lo = 0, hi = kElePixels - 1;
-        for (int i = 0; i < nl; i++) {
+        int lo = 0, hi = (kElePixels >> level) - 1;
+        for (int i = level; i < nl; i++) {
             const int ts = kElePixels >> i;
-            if (i > 0) { lo = (lo - 1) >> 1; hi = (hi >> 1) + 1; }            // relative to the tile's own square
+            if (i > level) { lo = (lo - 1) >> 1; hi = (hi >> 1) + 1; }        // relative to the tile's own square
             const int bd = nb ? 1 << (nl - 1 - i) : 0, l = std::max(lo, -bd), h = std::min(hi, ts - 1 + bd);
             b += (double)(h - l + 1) * (h - l + 1) * px;
             (void)ts;
@@ -1679,9 +1681,11 @@ bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const
         if (want_bgr && !blend_out_bgr_.reserve(tile_px * 3 * cn)) return false;
         if (!blend_src_.reserve(jobs.size() * sizeof(BlendJob))) return false;
         HIP_OK(hipMemcpyAsync(blend_src_.p, jobs.data(), jobs.size() * sizeof(BlendJob), hipMemcpyHostToDevice, stream_));
-        prof_begin(K_BLEND_FUSED, bytes);
-        launch_blend_fused(stream_, lay_, (const BlendJob*)blend_src_.p, (int)jobs.size(), raw_host ? blend_out_raw_.p : nullptr,
-                           want_bgr ? (uint8_t*)blend_out_bgr_.p : nullptr);
+        prof_begin(level ? K_BLEND_LEVEL : K_BLEND_FUSED, bytes);
+        if (level) launch_blend_level(stream_, lay_, level, (const BlendJob*)blend_src_.p, (int)jobs.size(), raw_host ? blend_out_raw_.p : nullptr,
+                                      want_bgr ? (uint8_t*)blend_out_bgr_.p : nullptr);
+        else launch_blend_fused(stream_, lay_, (const BlendJob*)blend_src_.p, (int)jobs.size(), raw_host ? blend_out_raw_.p : nullptr,
+                                want_bgr ? (uint8_t*)blend_out_bgr_.p : nullptr);
         prof_end();
         HIP_OK(hipGetLastError());
         if (jpeg) {
@@ -1843,6 +1847,34 @@ bool FusionMap::blend_list(const std::vector<std::pair<int, int>>& tiles, uint8_
     return blend_batch(tiles, nullptr, nullptr, bgr);
 }
 
+// The views of pyramid level `level` (pf_blend_tiles_level, pf_blend_changed_level, pf_save_to_memory_level): which levels a map has
+bool FusionMap::level_ok(const char* who, int level)
+{
+    const int top = single_band_ ? 0 : band_num_;
+    if (level < 0 || level > top) {
+        set_error(std::string(who) + ": level " + std::to_string(level) + " is outside 0 .. " + std::to_string(top) +
+                  (single_band_ ? " (a single-band map holds no pyramid)" : ""));
+        return false;
+    }
+    if (level > 0 && opt_.shard_count > 1) { set_error(std::string(who) + ": a sharded map (shard_count > 1) has views of level 0 only"); return false; }
+    return true;
+}
+
+// pf_blend_tiles_level: blend_list with the 8U and / or the raw view, at any level.  Level 0 is blend_list's own path
+bool FusionMap::blend_list_level(const std::vector<std::pair<int, int>>& tiles, int level, uint8_t* bgr, void* raw)
+{
+    if (!level_ok("pf_blend_tiles_level", level)) return false;
+    if (single_band_) {          // level 0: the tile as it is (see blend_tile); raw is its four bytes a pixel
+        const size_t n = (size_t)kElePixels * kElePixels;
+        for (size_t i = 0; i < tiles.size(); i++)
+            (void)blend_tile(tiles[i].first, tiles[i].second, raw ? (char*)raw + i * n * 4 : nullptr, bgr ? bgr + i * n * 3 : nullptr, nullptr);
+        return init_ok_;
+    }
+    std::lock_guard<std::mutex> l(mu_); (void)drain();
+    if (!init_ok_ || !set_device()) return false;
+    return blend_batch(tiles, nullptr, raw, bgr, nullptr, level);
+}
+
 bool FusionMap::blend_list_jpeg(const std::vector<std::pair<int, int>>& tiles, int quality, uint8_t* out, size_t cap, size_t* offsets)
 {
     if (single_band_) {          // the Map2DCPU tile is displayable as is (see blend_tile): assembled on the host, the host encoder
@@ -1863,9 +1895,10 @@ bool FusionMap::blend_list_jpeg(const std::vector<std::pair<int, int>>& tiles, i
     return blend_batch(tiles, nullptr, nullptr, nullptr, &tj);
 }
 
-// the draw() loop's texture refresh (.cpp:705-742) without GL
-int FusionMap::blend_changed(int* xy, uint8_t* bgr, int cap)
+// the draw() loop's texture refresh (.cpp:705-742) without GL; level > 0: the same tiles as views of that level, (256 >> level)^2 x 3 bytes each
+int FusionMap::blend_changed(int* xy, uint8_t* bgr, int cap, int level)
 {
+    if (!level_ok("pf_blend_changed_level", level)) return 0;
     std::lock_guard<std::mutex> l(mu_); (void)drain();
     if (!init_ok_ || !set_device()) return 0;
     std::vector<std::pair<int, int>> v;
@@ -1889,7 +1922,7 @@ int FusionMap::blend_changed(int* xy, uint8_t* bgr, int cap)
         }
         return (int)tiles.size();
     }
-    if (sync_all() != hipSuccess || !blend_batch(tiles, nullptr, nullptr, bgr)) return 0;
+    if (sync_all() != hipSuccess || !blend_batch(tiles, nullptr, nullptr, bgr, nullptr, level)) return 0;
     for (size_t i = 0; i < tiles.size(); i++) {
         xy[2 * i] = tiles[i].first; xy[2 * i + 1] = tiles[i].second;
         store_.find(tiles[i].first, tiles[i].second)->changed = false;
@@ -1915,10 +1948,11 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
     if (foreign) for (auto& f : *foreign) { cnt++; mnx = std::min(mnx, f.ix); mny = std::min(mny, f.iy); mxx = std::max(mxx, f.ix); mxy = std::max(mxy, f.iy); }
     if (!cnt) return false;
     const int wx = mxx + 1 - mnx, wy = mxy + 1 - mny;
-    t.rows = wy * kElePixels; t.cols = wx * kElePixels; t.tx0 = mnx; t.ty0 = mny;
+    const int level = t.level;                      // 0 but for pf_save_to_memory_level (checked there: Extent / Buffer without mask)
+    t.rows = wy * (kElePixels >> level); t.cols = wx * (kElePixels >> level); t.tx0 = mnx; t.ty0 = mny;
     for (double& v : t.transform) v = 0;
-    t.transform[0] = length_pixel_; t.transform[3] = min_[0] + (mnx - off_x_) * ele_size_;
-    t.transform[5] = length_pixel_; t.transform[7] = min_[1] + (mny - off_y_) * ele_size_;
+    t.transform[0] = length_pixel_ * (1 << level); t.transform[3] = min_[0] + (mnx - off_x_) * ele_size_;
+    t.transform[5] = length_pixel_ * (1 << level); t.transform[7] = min_[1] + (mny - off_y_) * ele_size_;
     t.transform[10] = 1; t.transform[15] = 1;
     if (t.kind == SaveTarget::Extent) return true;
     const bool file = t.kind == SaveTarget::File;
@@ -1956,7 +1990,7 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
     if (!blend_out_bgr_.reserve(out_bytes)) return false;
 #if PF_EXPERIMENTS
     static const bool per_level = exp_env("PF_BLEND_PER_LEVEL") != nullptr;
-    if (per_level && bgr && !mask) {                              // rounds 1-5: paste per level, one collapse launch per level, finish
+    if (per_level && bgr && !mask && level == 0) {                // rounds 1-5: paste per level, one collapse launch per level, finish
         for (int i = 0; i <= L; i++) {
             const size_t n = (size_t)(t.rows >> i) * (t.cols >> i);
             if (!blend_lv_[i].reserve(n * px)) return false;
@@ -1979,7 +2013,13 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
 #endif
     // one launch: paste, collapse in LDS, 8U, background (collapse_fused.hip).  Algorithmic bytes: every tile's Laplacians and
     // level-0 weights read once, the mosaic written once.
-    if (file || bgr) {
+    if (level > 0) {          // the same from level `level` down (collapse_level.hip): levels level .. L and that level's weights read
+        double P = 0; for (int i = level; i <= L; i++) P += 1.0 / (double)(1 << (2 * i));
+        prof_begin(K_SAVE_LEVEL, (double)cnt * kElePixels * kElePixels * (P * px + 4.0 / (double)(1 << (2 * level))) + (double)out_bytes);
+        launch_save_level(stream_, lay_, level, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
+        prof_end();
+        HIP_OK(hipGetLastError());
+    } else if (file || bgr) {
         double P = 0; for (int i = 0; i <= L; i++) P += 1.0 / (double)(1 << (2 * i));
         prof_begin(K_SAVE_FUSED, (double)cnt * kElePixels * kElePixels * (P * px + 4) + (double)out_bytes);
         launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
@@ -2015,6 +2055,17 @@ bool FusionMap::save_to_memory_mask(uint8_t* bgr, uint8_t* mask, int* rows, int*
 {
     SaveTarget t;
     t.kind = bgr || mask ? SaveTarget::Buffer : SaveTarget::Extent; t.bgr = bgr; t.mask = mask;
+    if (!save_mosaic(t)) return false;
+    *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
+    return true;
+}
+
+// the two-call protocol of pf_save_to_memory at pyramid level `level`: the extent is wy E x wx E, E = 256 >> level
+bool FusionMap::save_to_memory_level(int level, uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
+{
+    if (!level_ok("pf_save_to_memory_level", level)) return false;
+    SaveTarget t;
+    t.kind = bgr ? SaveTarget::Buffer : SaveTarget::Extent; t.bgr = bgr; t.level = level;
     if (!save_mosaic(t)) return false;
     *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
     return true;

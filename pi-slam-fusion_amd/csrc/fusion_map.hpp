@@ -130,6 +130,7 @@ public:
         uint8_t* mask = nullptr;
         std::vector<uint8_t>* mask_image = nullptr;
         bool masked = false;
+        int level = 0;                  // Extent / Buffer without mask only: the mosaic collapsed down to this pyramid level, (256 >> level)^2 pixels a tile
         // results
         int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
         double transform[16] = {};      // the ModelTransformationTag of a TIFF of this mosaic: pixel -> plane metres
@@ -143,6 +144,8 @@ public:
     bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0) { return save_to_memory_mask(bgr, nullptr, rows, cols, tx0, ty0); }
     // ... with the coverage beside the pixels (pf_save_to_memory_mask): both null reports the extent, either may be null after that
     bool save_to_memory_mask(uint8_t* bgr, uint8_t* mask, int* rows, int* cols, int* tx0, int* ty0);
+    // ... of the view of pyramid level `level` (pf_save_to_memory_level)
+    bool save_to_memory_level(int level, uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0);
 
     // seam exchange support (dist.cpp)
     using TileRec = pf::TileRec;        // dist_plan.hpp
@@ -185,8 +188,11 @@ public:
     bool get_tile_level(int ix, int iy, int level, void* lap, float* w);
     bool get_tile_bgra(int ix, int iy, uint8_t* bgra);
     bool blend_tile(int ix, int iy, void* raw, uint8_t* bgr, const void* const* halo);
-    int  blend_changed(int* xy, uint8_t* bgr, int cap);
+    int  blend_changed(int* xy, uint8_t* bgr, int cap, int level = 0);
     bool blend_list(const std::vector<std::pair<int, int>>& tiles, uint8_t* bgr);      // pf_blend_tiles: Ischanged left alone
+    // views of pyramid level `level` (collapse_level.hip): (256 >> level)^2 pixels a tile, bgr and / or raw (either may be null)
+    bool blend_list_level(const std::vector<std::pair<int, int>>& tiles, int level, uint8_t* bgr, void* raw);
+    bool level_ok(const char* who, int level);      // false, with the reason in last_error(): no such level / no pyramid / a sharded map above level 0
     // pf_blend_tiles_jpeg: the same tiles as n JPEG streams back to back, offsets[0..n]; the blended pixels stay in HBM
     struct TileJpeg { int quality; uint8_t* out; size_t cap; size_t* offsets; size_t used = 0; };
     bool blend_list_jpeg(const std::vector<std::pair<int, int>>& tiles, int quality, uint8_t* out, size_t cap, size_t* offsets);
@@ -221,7 +227,7 @@ private:
     void worker();                                                 // .cpp:619-635
     int  acquire_slot(size_t bytes);
     bool upload(const pf_image* img, int slot);
-    bool blend_batch(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg = nullptr);
+    bool blend_batch(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg = nullptr, int level = 0);
     // bytes: SURVEY 8d's algorithmic bytes of the launch for EVERY tile of the canvas; bytes_run (< 0: the same): those of the part of the
     // canvas its blocks actually process (the cull / a shard leave blocks out) -- the numerator of bench.py's roofline.frac
     void prof_begin(int id, double bytes, hipStream_t st = nullptr, double bytes_run = -1);

@@ -59,7 +59,7 @@ static_assert(sizeof(BlendJob) == 88, "BlendJob is copied to LDS by words");
 
 // kernel ids for the profile table
 enum KernelId { K_WARP = 0, K_PYRDOWN_IMG, K_PYRDOWN_W, K_LAP_SELECT, K_BLEND_GATHER, K_COLLAPSE,
-                K_BLEND_FINISH, K_MOSAIC_GATHER, K_SAVE_FINISH, K_LEVEL0, K_LEVEL, K_SINGLE, K_BLEND_FUSED, K_SAVE_FUSED, K_COUNT };
+                K_BLEND_FINISH, K_MOSAIC_GATHER, K_SAVE_FINISH, K_LEVEL0, K_LEVEL, K_SINGLE, K_BLEND_FUSED, K_SAVE_FUSED, K_BLEND_LEVEL, K_SAVE_LEVEL, K_COUNT };
 const char* kernel_name(int id);
 
 void launch_warp(hipStream_t s, bool f32, const uint8_t* src, const WarpArgs& a, void* g0, float* w0);
@@ -118,6 +118,10 @@ int  level_block_rows(bool f32);                                     // block he
 // (collapse_fused.hip).  jobs_dev / table_dev in device memory; raw_out (pyramid type, n x 256 x 256 x 3) and bgr_out may be null
 void launch_blend_fused(hipStream_t s, const TileLayout& lay, const BlendJob* jobs_dev, int n, void* raw_out, uint8_t* bgr_out);
 void launch_save_fused(hipStream_t s, const TileLayout& lay, const uint64_t* table_dev, int wx, int wy, int bg, uint8_t* bgr_out);
+// The same two truncated at pyramid level `level`, 1 <= level <= nlev - 1 (collapse_level.hip): levels level .. L collapsed, tiles of
+// E = 256 >> level pixels, masked by the weights of that level.  raw_out / bgr_out: n x E x E x 3; the mosaic: wy E x wx E x 3
+void launch_blend_level(hipStream_t s, const TileLayout& lay, int level, const BlendJob* jobs_dev, int n, void* raw_out, uint8_t* bgr_out);
+void launch_save_level(hipStream_t s, const TileLayout& lay, int level, const uint64_t* table_dev, int wx, int wy, int bg, uint8_t* bgr_out);
 
 // The per-level form of rounds 1-5 (one padded square per level in HBM, one launch per reference op): kept in the experiments library
 // as the A/B partner and second opinion of the fused kernel (PF_BLEND_PER_LEVEL=1, tests/test_gpu_variants.py)

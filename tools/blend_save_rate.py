@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Output side of the path on the bench mosaic (dev tool): Ele::blend of every changed tile and save().
-usage: tools/blend_save_rate.py [--int16] [--frames N] [--reps R]
+usage: tools/blend_save_rate.py [--int16] [--frames N] [--reps R] [--level K[,K...] [--rounds N]]
 Prints wall times into a fresh pageable buffer (first touch included), a touched pageable buffer and a page-locked one, and the
-kernels' own time and algorithmic rate from the profile table."""
+kernels' own time and algorithmic rate from the profile table.
+--level: the reduced-resolution views instead (level 0 = the existing path).  Every round measures each listed level in turn on the
+same map (interleaved, one process, one box): the kernel by HIP events, blend_tiles and save_to_memory into page-locked buffers by
+wall clock; then the slowest / fastest round per level."""
 import argparse, importlib, os, sys, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 import bench
 ap = argparse.ArgumentParser(); ap.add_argument("--int16", action="store_true"); ap.add_argument("--frames", type=int, default=120)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--level", default=None, help="comma-separated pyramid levels of the views to measure"); ap.add_argument("--rounds", type=int, default=5)
 a = ap.parse_args()
 import numpy as np, torch
 pf = bench.load_package(); wl = importlib.import_module("pi_slam_fusion_amd.workloads")
@@ -23,6 +27,34 @@ for k in range(a.frames):
 m.sync()
 nt = len(m.tiles())
 m.profile_reset(); m.profile_enable(1)
+def level_rounds(levels, rounds):
+    tiles = m.tiles()
+    kern = lambda name: (lambda v: v["ms"] / max(v["launches"], 1))(m.profile_read()[name])
+    bufs = {k: pf.host_array((len(tiles), 256 >> k, 256 >> k, 3)) for k in levels}
+    keep = {}
+    def alloc(shape):
+        if shape not in keep: keep[shape] = pf.host_array(shape)
+        return keep[shape]
+    for k in levels:                                  # warm-up: buffers, page-locked registrations, first launches
+        assert m.blend_tiles(tiles, out=bufs[k], level=k) is not None and m.save_to_memory(alloc=alloc, level=k) is not None
+    res = {k: [] for k in levels}
+    for r in range(rounds):
+        for k in levels:
+            m.profile_reset()
+            t0 = time.perf_counter(); m.blend_tiles(tiles, out=bufs[k], level=k); t1 = time.perf_counter()
+            kb = kern("blend_level" if k else "blend_fused"); m.profile_reset()
+            t2 = time.perf_counter(); img = m.save_to_memory(alloc=alloc, level=k); t3 = time.perf_counter()
+            ks = kern("save_level" if k else "save_fused")
+            res[k].append((kb, (t1 - t0) * 1e3, ks, (t3 - t2) * 1e3))
+            print("round %d level %d: blend kernel %.3f ms, blend_tiles wall %.2f ms (%d tiles, %.1f MB); save kernel %.3f ms, save_to_memory wall %.2f ms (%d x %d)" %
+                  (r, k, kb, (t1 - t0) * 1e3, len(tiles), bufs[k].nbytes / 1e6, ks, (t3 - t2) * 1e3, img[0].shape[1], img[0].shape[0]))
+    for k in levels:
+        a_ = np.array(res[k])
+        print("level %d  min / max over %d rounds: blend kernel %.3f / %.3f ms, blend_tiles wall %.2f / %.2f ms, save kernel %.3f / %.3f ms, save_to_memory wall %.2f / %.2f ms" %
+              ((k, rounds) + tuple(v for c in range(4) for v in (a_[:, c].min(), a_[:, c].max()))))
+if a.level is not None:
+    level_rounds([int(v) for v in a.level.split(",")], a.rounds)
+    sys.exit(0)
 def dump():
     for n, v in m.profile_read().items():
         if v["launches"]:
