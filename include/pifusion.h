@@ -312,6 +312,69 @@ int     pf_format_map_update(const double plane[7], const double gps_origin[3], 
 int     pf_map_update_command(pf_map* m, int ix, int iy, const double gps_origin[3], char* out, int cap);
 /* pi::calcLngLatFromDistance (utils_GPS.cpp:133-160) alone */
 void    pf_lnglat_from_distance(double lng1, double lat1, double dx, double dy, double* lng2, double* lat2);
+
+/* --- north-up Web-Mercator map tiles (EPSG:3857, the XYZ / OSM slippy-map numbering z/x/y, 256 x 256 pixels), resampled on the GPU ---
+ * What a web map, QGIS or a ground station loads as it is.  Every other output lives in the fitted ground plane's own frame; these
+ * are placed on the globe by the plane pose and GPS.Origin, exactly as pf_format_map_update places a tile's corners.
+ *
+ * px2ll[6]: the affine from a CONTINUOUS mosaic pixel coordinate (column, row) to degrees, lng = P0 + P1 col + P2 row,
+ * lat = P3 + P4 col + P5 row; pixel (i, j) covers [i, i + 1) x [j, j + 1) (RasterPixelIsArea, as the TIFF declares).
+ * pf_webtiles_georef: px2ll of the mosaic pf_save_to_memory would report at that moment (its rows and cols are returned too):
+ * pf_save_tiff's pixel -> plane metres, the plane pose (East = world x, North = world y), pf_lnglat_from_distance around gps_origin --
+ * pf_webtiles_georef_compose is that chain alone, from the 16 doubles of the TIFF's ModelTransformationTag.  0 with the reason in
+ * pf_last_error() for a map without content, a sharded map (shard_count > 1: gather with pf_dist_save_to_memory on rank 0 and hand
+ * the mosaic to pf_webtiles_device) and a singular affine (a vertical plane).
+ *
+ * With n = 256 * 2^z, global pixel column c and row r have their centres at lng_c = (c + 0.5) / n * 360 - 180 and
+ * lat_r = atan(sinh(pi (1 - 2 (r + 0.5) / n))) * 180 / pi.  pf_webtiles_plan: range = {tx0, ty0, tx1, ty1}, the inclusive range of
+ * tiles the bounding box of the four image corners touches at zoom z, and -- A being the inverse of the 2 x 2 part of px2ll -- the tables
+ * UX[c] = A00 (lng_c - P0) - 0.5, UY[c] = A10 (lng_c - P0) - 0.5 over the 256 (tx1 - tx0 + 1) columns and VX[r] = A01 (lat_r - P3),
+ * VY[r] = A11 (lat_r - P3) over the 256 (ty1 - ty0 + 1) rows of the range: output pixel (c, r) samples the source at pixel-index
+ * position (UX[c] + VX[r], UY[c] + VY[r]).  Refuses z outside 0 .. 24, a singular affine, a corner beyond 85.05 degrees of latitude
+ * (nothing is written) and tables smaller than needed (cap_cols, cap_rows doubles each: the range alone is written and says what is
+ * needed); with all four tables NULL it is asked for the range alone and returns 1.  pf_webtiles_native_zoom: the smallest z at which one source pixel spans at least 1 / sqrt 2 output pixel at the image
+ * centre (sqrt |det| of d(global pixel) / d(source pixel)); -1 where pf_webtiles_plan would refuse.
+ *
+ * The tiles of zmax are sampled from the mosaic and its coverage: x0 = floor(sx), fx = floor((sx - x0) 256) (at most 255), the same
+ * for y; four taps with weights (256 - fx, fx) x (256 - fy, fy); a tap counts when it lies inside the image and its mask is not 0;
+ * den = the weights that count; 2 den < 65536: the background colour (bg saturated to 0 .. 255), uncovered; otherwise every channel
+ * is (sum of w p + den / 2) / den, covered.  A tile of zoom z - 1 is made from its four children: a pixel is (sum + (k >> 1)) / k over
+ * the k covered of the 2 x 2 pixels under it, covered when k > 0.  A tile without a covered pixel is not handed over and counts as
+ * an absent child.  Every tile handed over carries its JPEG stream (byte-equal to pf_jpeg_encode_bgr(tile, 256, 256, 0, quality)), its
+ * cover class (1: partly covered, 2: fully) and, partly covered, its mask: 8192 bytes, 32 a row, bit 7 of byte 0 = column 0, 1 = covered.
+ * zmax < 0: the native zoom; zmin < 0: the first zoom, going down, at which the range is a single tile.  The pointers of a pf_webtile
+ * are valid during the sink's call; the sink runs on the caller's thread while the library holds the map (pf_webtiles) or its device
+ * encoder (pf_webtiles_device), so it must not call back into either; a sink that returns 0 stops the export, which then returns 0.
+ * pf_webtiles_device: image (BGR8, step bytes a row, 0 = packed) and mask (a byte per pixel, mask_step a row) in device memory, the
+ * work queued on hip_stream.  pf_webtiles: the map's mosaic of that moment -- drain, extent, collapse and coverage under one hold of
+ * the map as for every save; a TypeCPU / TypeGPU map goes through its host mosaic and alpha mask.  pf_save_webtiles: dir/z/x/y.jpg, for a
+ * partly covered tile dir/z/x/y.pbm beside it (P4, 1 = covered), and dir/tiles.json: bounds in degrees, minzoom, maxzoom and per zoom the
+ * tile range and counts.  On failure it returns 0, names the tile in pf_last_error() and leaves what it wrote.
+ * Device memory does not grow with the mosaic beyond a fixed batch (8 x 8 tiles of zmax and their three zooms of ancestors) plus the
+ * tiles of the zooms <= zmax - 3.  pf_debug_webtiles_batch: test hook, the batch's edge in tiles (8, 4 or 2); returns the edge set. */
+typedef struct pf_webtile {
+    int z, x, y, cover;
+    const uint8_t* jpeg;
+    size_t jpeg_len;
+    const uint8_t* mask8192;   /* NULL when the tile is fully covered */
+    const uint8_t* bgr;        /* NULL unless pixels were asked for   */
+} pf_webtile;
+typedef int (*pf_webtile_sink)(void* user, const pf_webtile* t);   /* 0 stops the export */
+int     pf_webtiles_georef(pf_map* m, const double gps_origin[3], double px2ll[6], int* rows, int* cols);
+int     pf_webtiles_georef_compose(const double model_transform[16], const double plane[7], const double gps_origin[3], double px2ll[6]);
+int     pf_webtiles_plan(const double px2ll[6], int rows, int cols, int z, int range[4], double* ux, double* uy, double* vx, double* vy,
+                         long long cap_cols, long long cap_rows);
+int     pf_webtiles_native_zoom(const double px2ll[6], int rows, int cols);
+int     pf_webtiles_device(const void* dev_bgr, int rows, int cols, size_t step, const void* dev_mask, size_t mask_step,
+                           const double px2ll[6], int zmin, int zmax, int quality, int bg,
+                           int want_pixels, pf_webtile_sink sink, void* user, void* hip_stream);
+int     pf_webtiles(pf_map* m, const double gps_origin[3], int zmin, int zmax, int quality, int want_pixels, pf_webtile_sink sink, void* user);
+int     pf_save_webtiles(pf_map* m, const char* dir, const double gps_origin[3], int zmin, int zmax, int quality);
+int     pf_debug_webtiles_batch(int edge);
+/* test / measurement hook: while on, HIP events bracket the sample kernel, the reduce kernel and the encoder of every export;
+ * pf_debug_webtiles_timing_read: their milliseconds in the most recent export and the number of tiles it sampled */
+void    pf_debug_webtiles_timing(int on);
+void    pf_debug_webtiles_timing_read(double out4[4]);
 /* unused-by-the-reference helpers kept for API completeness (.cpp:57-75)   */
 int     pf_normalize_using_weight_map(const float* weight, float* src3, size_t npix);
 int     pf_mul_weight_map(const float* weight, float* src3, size_t npix);

@@ -165,6 +165,10 @@ public:
     bool saveTiff(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
     // the pyramid TIFF with a transparency mask behind every image: covered where the level-0 weight is not 0 (pf_save_tiff_masked)
     bool saveMasked(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff_masked(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
+    // north-up Web-Mercator map tiles dir/z/x/y.jpg (+ .pbm coverage of partly covered tiles, tiles.json) around GPS.Origin (pf_save_webtiles);
+    // zmax < 0: the native zoom, zmin < 0: down to the zoom at which one tile holds the mosaic
+    bool saveWebTiles(const std::string& dir, const double gpsOrigin[3], int zmin = -1, int zmax = -1, int quality = 95)
+    { return pf_save_webtiles(h_, dir.c_str(), gpsOrigin, zmin, zmax, quality) != 0; }
     unsigned queueSize() { return pf_queue_size(h_); }
     bool sync() { return pf_sync(h_) != 0; }
 

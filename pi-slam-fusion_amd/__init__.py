@@ -58,6 +58,15 @@ class DistStats(C.Structure):
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                           C.POINTER(C.c_size_t), C.c_int)
 
+
+class WebTile(C.Structure):
+    """pf_webtile: one map tile on its way through a sink"""
+    _fields_ = [("z", C.c_int), ("x", C.c_int), ("y", C.c_int), ("cover", C.c_int), ("jpeg", C.POINTER(C.c_uint8)), ("jpeg_len", C.c_size_t),
+                ("mask8192", C.POINTER(C.c_uint8)), ("bgr", C.POINTER(C.c_uint8))]
+
+
+WEBTILE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(WebTile))
+
 _lib = None
 
 
@@ -117,6 +126,17 @@ def lib():
         L.pf_tiff_write_device_masked.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, dp, C.c_int, vp]
         L.pf_save_tiff_masked.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
         L.pf_save_to_memory_mask.argtypes = [vp, vp, vp, ip, ip, ip, ip]
+    if hasattr(L, "pf_webtiles") or not os.environ.get("PF_LIB"):
+        L.pf_webtiles_georef.argtypes = [vp, dp, dp, ip, ip]
+        L.pf_webtiles_georef_compose.argtypes = [dp, dp, dp, dp]
+        L.pf_webtiles_plan.argtypes = [dp, C.c_int, C.c_int, C.c_int, ip, dp, dp, dp, dp, C.c_longlong, C.c_longlong]
+        L.pf_webtiles_native_zoom.argtypes = [dp, C.c_int, C.c_int]
+        L.pf_webtiles_device.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, WEBTILE_SINK, vp, vp]
+        L.pf_webtiles.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, WEBTILE_SINK, vp]
+        L.pf_save_webtiles.argtypes = [vp, C.c_char_p, dp, C.c_int, C.c_int, C.c_int]
+        L.pf_debug_webtiles_batch.argtypes = [C.c_int]
+        L.pf_debug_webtiles_timing.argtypes = [C.c_int]; L.pf_debug_webtiles_timing.restype = None
+        L.pf_debug_webtiles_timing_read.argtypes = [dp]; L.pf_debug_webtiles_timing_read.restype = None
     L.pf_debug_jpeg_huffman.argtypes = [vp, C.POINTER(C.c_longlong)]; L.pf_debug_jpeg_huffman.restype = None
     L.pf_feed_jpeg_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), dp, C.c_int, ip]
     L.pf_num_levels.argtypes = [vp]
@@ -380,6 +400,72 @@ def jpeg_huffman_counts(map2d=None):
     return tuple(out)
 
 
+def _d(values, n):
+    a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    if a.size != n:
+        raise ValueError("%d doubles expected" % n)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def webtiles_georef_compose(model_transform, plane, gps_origin):
+    """px2ll (6 doubles: lng = P0 + P1 col + P2 row, lat = P3 + P4 col + P5 row) of a mosaic whose TIFF would carry model_transform (16
+    doubles, pixel -> plane metres), on the plane `plane` around gps_origin (pf_webtiles_georef_compose); None for a singular affine"""
+    (_, t), (_, p), (_, g) = _d(model_transform, 16), _d(plane, 7), _d(gps_origin, 3)
+    out = np.zeros(6)
+    return out if lib().pf_webtiles_georef_compose(t, p, g, out.ctypes.data_as(C.POINTER(C.c_double))) else None
+
+
+def webtiles_native_zoom(px2ll, rows, cols):
+    """the smallest zoom at which a source pixel spans at least 1 / sqrt 2 output pixel (pf_webtiles_native_zoom); -1: no such plan"""
+    _, p = _d(px2ll, 6)
+    return int(lib().pf_webtiles_native_zoom(p, rows, cols))
+
+
+def webtiles_plan(px2ll, rows, cols, z):
+    """((tx0, ty0, tx1, ty1), UX, UY, VX, VY) of pf_webtiles_plan: the inclusive tile range of zoom z and the tables over its global
+    columns and rows -- output pixel (c, r) samples the source at (UX[c] + VX[r], UY[c] + VY[r]).  Raises ValueError on a refusal"""
+    L = lib(); _, p = _d(px2ll, 6)
+    rg = (C.c_int * 4)(-1, -1, -1, -1)
+    if not L.pf_webtiles_plan(p, rows, cols, z, rg, None, None, None, None, 0, 0):          # without tables: the range alone, which says what is needed
+        raise ValueError(L.pf_last_error().decode())
+    nc, nr = 256 * (rg[2] - rg[0] + 1), 256 * (rg[3] - rg[1] + 1)
+    ux, uy, vx, vy = np.empty(nc), np.empty(nc), np.empty(nr), np.empty(nr)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    if not L.pf_webtiles_plan(p, rows, cols, z, rg, ptr(ux), ptr(uy), ptr(vx), ptr(vy), nc, nr):
+        raise ValueError(L.pf_last_error().decode())
+    return tuple(rg), ux, uy, vx, vy
+
+
+def _collect_webtiles(call, pixels):
+    """runs call(sink) and returns the records the sink saw: dicts z, x, y, cover (1 partial, 2 full), jpeg (bytes), mask (256 x 256 bool,
+    None for a fully covered tile), and bgr (256 x 256 x 3) when pixels were asked for"""
+    out = []
+
+    def sink(user, t):
+        t = t.contents
+        rec = {"z": t.z, "x": t.x, "y": t.y, "cover": t.cover, "jpeg": C.string_at(t.jpeg, t.jpeg_len), "mask": None}
+        if t.mask8192:
+            rec["mask"] = np.unpackbits(np.frombuffer(C.string_at(t.mask8192, 8192), np.uint8)).reshape(256, 256).astype(bool)
+        if pixels and t.bgr:
+            rec["bgr"] = np.frombuffer(C.string_at(t.bgr, 256 * 256 * 3), np.uint8).reshape(256, 256, 3).copy()
+        out.append(rec)
+        return 1
+
+    cb = WEBTILE_SINK(sink)
+    if not call(cb):
+        raise RuntimeError(lib().pf_last_error().decode())
+    return out
+
+
+def webtiles_device(dev_ptr, rows, cols, dev_mask, px2ll, zmin=None, zmax=None, quality=95, bg=0, pixels=False, step=0, mask_step=0, stream=None):
+    """North-up Web-Mercator map tiles (z/x/y, 256 x 256) of rows x cols BGR8 pixels and a byte-per-pixel coverage at device addresses,
+    placed by px2ll (pf_webtiles_device, csrc/webtiles.hip): the list of records of every tile with a covered pixel, zmax (None: the
+    native zoom) down to zmin (None: the zoom at which one tile holds the image)."""
+    _, p = _d(px2ll, 6)
+    return _collect_webtiles(lambda cb: lib().pf_webtiles_device(dev_ptr, rows, cols, step, dev_mask, mask_step, p, -1 if zmin is None else zmin, -1 if zmax is None else zmax,
+                                                                 quality, bg, int(pixels), cb, None, stream), pixels)
+
+
 def tile_owner(opt, ix, iy):
     return lib().pf_tile_owner(C.byref(opt), ix, iy)
 
@@ -510,6 +596,52 @@ class Map2D:
                 return None
             if (r.value, c.value) == want:
                 return out, mask, (x0.value, y0.value)
+
+    def webtiles_georef(self, gps_origin):
+        """(px2ll, rows, cols) of the mosaic save_to_memory would return now, around gps_origin = (lng, lat, alt) (pf_webtiles_georef);
+        None for an empty or sharded map or a vertical plane"""
+        _, g = _d(gps_origin, 3)
+        out = np.zeros(6); r, c = C.c_int(), C.c_int()
+        if not lib().pf_webtiles_georef(self._h, g, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r), C.byref(c)):
+            return None
+        return out, r.value, c.value
+
+    def webtiles(self, gps_origin, zmin=None, zmax=None, quality=95, pixels=False):
+        """The mosaic of this moment as north-up Web-Mercator map tiles (pf_webtiles): yields the records of webtiles_device"""
+        _, g = _d(gps_origin, 3)
+        for rec in _collect_webtiles(lambda cb: lib().pf_webtiles(self._h, g, -1 if zmin is None else zmin, -1 if zmax is None else zmax, quality, int(pixels), cb, None), pixels):
+            yield rec
+
+    def save_webtiles(self, dir, gps_origin, zmin=None, zmax=None, quality=95):
+        """dir/z/x/y.jpg, dir/z/x/y.pbm (coverage of the partly covered tiles) and dir/tiles.json (pf_save_webtiles)"""
+        _, g = _d(gps_origin, 3)
+        return bool(lib().pf_save_webtiles(self._h, str(dir).encode(), g, -1 if zmin is None else zmin, -1 if zmax is None else zmax, quality))
+
+    def export_mbtiles(self, path, gps_origin, zmin=None, zmax=None, quality=95, name="mosaic"):
+        """The same tiles as an MBTiles file (sqlite3): tables tiles (TMS rows: tile_row = 2^z - 1 - y) and metadata (format jpg, bounds,
+        minzoom, maxzoom).  Returns the number of tiles written"""
+        import sqlite3
+        geo = self.webtiles_georef(gps_origin)
+        if geo is None:
+            raise RuntimeError(lib().pf_last_error().decode())
+        recs = list(self.webtiles(gps_origin, zmin, zmax, quality))
+        p, rows, cols = geo
+        lng = [p[0] + p[1] * c + p[2] * r for c in (0, cols) for r in (0, rows)]
+        lat = [p[3] + p[4] * c + p[5] * r for c in (0, cols) for r in (0, rows)]
+        db = sqlite3.connect(str(path))
+        try:
+            db.execute("CREATE TABLE tiles (zoom_level INTEGER, tile_column INTEGER, tile_row INTEGER, tile_data BLOB)")
+            db.execute("CREATE UNIQUE INDEX tile_index ON tiles (zoom_level, tile_column, tile_row)")
+            db.execute("CREATE TABLE metadata (name TEXT, value TEXT)")
+            db.executemany("INSERT INTO tiles VALUES (?, ?, ?, ?)", [(t["z"], t["x"], (1 << t["z"]) - 1 - t["y"], t["jpeg"]) for t in recs])
+            zs = [t["z"] for t in recs]
+            meta = {"name": name, "format": "jpg", "type": "overlay", "version": "1", "bounds": "%.8f,%.8f,%.8f,%.8f" % (min(lng), min(lat), max(lng), max(lat)),
+                    "minzoom": str(min(zs)), "maxzoom": str(max(zs))}
+            db.executemany("INSERT INTO metadata VALUES (?, ?)", sorted(meta.items()))
+            db.commit()
+        finally:
+            db.close()
+        return len(recs)
 
     def save_to_memory(self, alloc=None, level=0):
         """(mosaic BGR8, (tile x0, tile y0)); alloc(shape) -> uint8 array supplies the buffer (e.g. host_array).  level=k: the

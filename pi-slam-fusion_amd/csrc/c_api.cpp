@@ -1,6 +1,11 @@
 // c_api.cpp -- extern "C" surface of libpifusion.so (include/pifusion.h).
 #include "dist.hpp"
 #include "jpeg_device.hpp"
+#include "webtiles_plan.hpp"
+#include <cerrno>
+#include <map>
+#include <string>
+#include <sys/stat.h>
 #include <cstdlib>
 #include <cmath>
 #include <cstdio>
@@ -347,6 +352,123 @@ int pf_map_update_command(pf_map* m, int ix, int iy, const double gps_origin[3],
     double plane[7], mn[2], ele; int x, y;
     if (!m->impl.map_update_inputs(ix, iy, plane, mn, &ele, &x, &y)) return 0;
     return pf_format_map_update(plane, gps_origin, mn[0], mn[1], ele, x, y, out, cap);
+}
+
+// --- Web-Mercator map tiles (webtiles_plan.hpp: the plan, pure host code; webtiles.hip: the kernels and the pyramid)
+int pf_webtiles_georef_compose(const double model_transform[16], const double plane[7], const double gps_origin[3], double px2ll[6])
+{
+    if (!model_transform || !plane || !gps_origin || !px2ll) { pf::set_error("pf_webtiles_georef_compose: a null argument"); return 0; }
+    double p[6], A[4];
+    pf::webtiles::georef_compose(model_transform, plane, gps_origin, p);
+    if (!pf::webtiles::invert2(p, A)) { pf::set_error(std::string("pf_webtiles_georef_compose: ") + pf::webtiles::plan_message(pf::webtiles::kPlanSingular)); return 0; }
+    std::memcpy(px2ll, p, sizeof p);
+    return 1;
+}
+int pf_webtiles_georef(pf_map* m, const double gps_origin[3], double px2ll[6], int* rows, int* cols)
+{
+    if (!m || !gps_origin || !px2ll) { pf::set_error("pf_webtiles_georef: no map, no origin or no result"); return 0; }
+    return m->impl.webtiles_georef(gps_origin, px2ll, rows, cols);
+}
+int pf_webtiles_plan(const double px2ll[6], int rows, int cols, int z, int range[4], double* ux, double* uy, double* vx, double* vy, long long cap_cols, long long cap_rows)
+{
+    const pf::webtiles::PlanResult r = pf::webtiles::plan(px2ll, rows, cols, z, range, ux, uy, vx, vy, cap_cols, cap_rows);
+    if (r != pf::webtiles::kPlanOk) { pf::set_error(std::string("pf_webtiles_plan: ") + pf::webtiles::plan_message(r)); return 0; }
+    return 1;
+}
+int pf_webtiles_native_zoom(const double px2ll[6], int rows, int cols) { return pf::webtiles::native_zoom(px2ll, rows, cols); }
+int pf_debug_webtiles_batch(int edge) { pf::webtiles_set_batch(edge); return pf::webtiles_batch(); }
+void pf_debug_webtiles_timing(int on) { pf::webtiles_set_timing(on != 0); }
+void pf_debug_webtiles_timing_read(double out4[4]) { if (out4) pf::webtiles_last_timing(out4); }
+int pf_webtiles_device(const void* dev_bgr, int rows, int cols, size_t step, const void* dev_mask, size_t mask_step, const double px2ll[6], int zmin, int zmax, int quality, int bg,
+                       int want_pixels, pf_webtile_sink sink, void* user, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_jpeg_mu);
+    if (!dev_bgr || !dev_mask || !px2ll || !sink || rows <= 0 || cols <= 0) { pf::set_error("pf_webtiles_device: no image, no mask, no georeference, no sink or a size that is not positive"); return 0; }
+    if ((step && step < (size_t)cols * 3) || (mask_step && mask_step < (size_t)cols)) { pf::set_error("pf_webtiles_device: step is smaller than a row"); return 0; }
+    hipPointerAttribute_t at{}, am{};
+    if (hipPointerGetAttributes(&at, dev_bgr) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_webtiles_device: the image is not in device memory"); return 0; }
+    if (hipPointerGetAttributes(&am, dev_mask) != hipSuccess || am.type != hipMemoryTypeDevice || am.device != at.device) {
+        (void)hipGetLastError(); pf::set_error("pf_webtiles_device: the mask is not in device memory beside the image"); return 0;
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_webtiles_device: hipSetDevice failed"); return 0; }
+    const int ok = pf::webtiles_export(dev_bgr, rows, cols, step, dev_mask, mask_step, px2ll, zmin, zmax, quality, bg, want_pixels != 0, sink, user, *shared_jpeg_encoder(at.device), (hipStream_t)hip_stream);
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
+int pf_webtiles(pf_map* m, const double gps_origin[3], int zmin, int zmax, int quality, int want_pixels, pf_webtile_sink sink, void* user)
+{
+    if (!m || !gps_origin || !sink) { pf::set_error("pf_webtiles: no map, no origin or no sink"); return 0; }
+    const FusionMap::WebTilesJob job{ gps_origin, zmin, zmax, quality, want_pixels != 0, sink, user, nullptr };
+    return m->impl.webtiles(job);
+}
+
+// pf_save_webtiles: the sink that writes dir/z/x/y.jpg (+ .pbm) and counts for tiles.json
+namespace {
+struct WebDir {
+    std::string dir, failed;
+    struct Zoom { int x0 = 0, y0 = 0, x1 = 0, y1 = 0; long long tiles = 0, partial = 0; };
+    std::map<int, Zoom> zooms;
+    static bool make_dir(const std::string& d) { return ::mkdir(d.c_str(), 0777) == 0 || errno == EEXIST; }
+    static bool write_file(const std::string& name, const char* head, const uint8_t* data, size_t len)
+    {
+        std::FILE* f = std::fopen(name.c_str(), "wb");
+        if (!f) return false;
+        bool ok = (!head || std::fputs(head, f) >= 0) && std::fwrite(data, 1, len, f) == len;
+        ok = std::fclose(f) == 0 && ok;
+        return ok;
+    }
+    static int sink(void* user, const pf_webtile* t)
+    {
+        WebDir& w = *(WebDir*)user;
+        const std::string dz = w.dir + "/" + std::to_string(t->z), dx = dz + "/" + std::to_string(t->x), stem = dx + "/" + std::to_string(t->y);
+        if (!make_dir(dz) || !make_dir(dx) || !write_file(stem + ".jpg", nullptr, t->jpeg, t->jpeg_len) ||
+            (t->mask8192 && !write_file(stem + ".pbm", "P4\n256 256\n", t->mask8192, 8192))) { w.failed = stem; return 0; }
+        Zoom& q = w.zooms[t->z];
+        if (!q.tiles) { q.x0 = q.x1 = t->x; q.y0 = q.y1 = t->y; }
+        q.x0 = std::min(q.x0, t->x); q.x1 = std::max(q.x1, t->x); q.y0 = std::min(q.y0, t->y); q.y1 = std::max(q.y1, t->y);
+        q.tiles++; q.partial += t->cover == 1;
+        return 1;
+    }
+};
+}  // namespace
+
+int pf_save_webtiles(pf_map* m, const char* dir, const double gps_origin[3], int zmin, int zmax, int quality)
+{
+    if (!m || !dir || !gps_origin) { pf::set_error("pf_save_webtiles: no map, no directory or no origin"); return 0; }
+    WebDir w;
+    w.dir = dir;
+    if (!WebDir::make_dir(w.dir)) { pf::set_error("pf_save_webtiles: cannot create " + w.dir); return 0; }
+    double rep[8] = {};
+    const FusionMap::WebTilesJob job{ gps_origin, zmin, zmax, quality, false, &WebDir::sink, &w, rep };
+    if (!m->impl.webtiles(job)) {
+        if (!w.failed.empty()) pf::set_error("pf_save_webtiles: cannot write tile " + w.failed);
+        return 0;
+    }
+    // the bounds: the box of the four image corners, in degrees
+    double west = 0, east = 0, south = 0, north = 0;
+    for (int k = 0; k < 4; k++) {
+        const double c = (k & 1) ? rep[7] : 0.0, r = (k & 2) ? rep[6] : 0.0;
+        const double lng = rep[0] + rep[1] * c + rep[2] * r, lat = rep[3] + rep[4] * c + rep[5] * r;
+        if (!k) { west = east = lng; south = north = lat; }
+        west = std::min(west, lng); east = std::max(east, lng); south = std::min(south, lat); north = std::max(north, lat);
+    }
+    const std::string name = w.dir + "/tiles.json";
+    std::FILE* f = std::fopen(name.c_str(), "w");
+    if (!f) { pf::set_error("pf_save_webtiles: cannot open " + name); return 0; }
+    std::fprintf(f, "{\n  \"scheme\": \"xyz\", \"crs\": \"EPSG:3857\", \"format\": \"jpg\", \"tile_size\": 256, \"mask_format\": \"pbm\",\n");
+    std::fprintf(f, "  \"bounds\": [%.10f, %.10f, %.10f, %.10f],\n", west, south, east, north);
+    std::fprintf(f, "  \"minzoom\": %d, \"maxzoom\": %d,\n  \"zooms\": [", w.zooms.empty() ? 0 : w.zooms.begin()->first, w.zooms.empty() ? 0 : w.zooms.rbegin()->first);
+    bool first = true;
+    for (auto& kv : w.zooms) {
+        std::fprintf(f, "%s\n    {\"z\": %d, \"x0\": %d, \"y0\": %d, \"x1\": %d, \"y1\": %d, \"tiles\": %lld, \"partial\": %lld}", first ? "" : ",", kv.first, kv.second.x0, kv.second.y0,
+                     kv.second.x1, kv.second.y1, kv.second.tiles, kv.second.partial);
+        first = false;
+    }
+    std::fprintf(f, "\n  ]\n}\n");
+    if (std::fclose(f) != 0) { pf::set_error("pf_save_webtiles: cannot write " + name); return 0; }
+    return 1;
 }
 
 void pf_se3_inverse(const double a[7], double out[7]) { from_pose(pf::inverse(to_pose(a)), out); }

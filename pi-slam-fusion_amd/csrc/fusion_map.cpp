@@ -1,6 +1,7 @@
 // fusion_map.cpp -- host engine: prepare / feed / renderFrame / blend / save on
 // the GPU, following the control flow of Map2DFusion/MultiBandMap2DCPU.cpp.
 #include "fusion_map.hpp"
+#include "webtiles_plan.hpp"
 #include "env.hpp"
 #include "warp_index.hpp"
 #include "coverage.hpp"
@@ -1947,6 +1948,7 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
     });
     if (foreign) for (auto& f : *foreign) { cnt++; mnx = std::min(mnx, f.ix); mny = std::min(mny, f.iy); mxx = std::max(mxx, f.ix); mxy = std::max(mxy, f.iy); }
     if (!cnt) return false;
+    t.found = true;
     const int wx = mxx + 1 - mnx, wy = mxy + 1 - mny;
     const int level = t.level;                      // 0 but for pf_save_to_memory_level (checked there: Extent / Buffer without mask)
     t.rows = wy * (kElePixels >> level); t.cols = wx * (kElePixels >> level); t.tx0 = mnx; t.ty0 = mny;
@@ -1954,8 +1956,10 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
     t.transform[0] = length_pixel_ * (1 << level); t.transform[3] = min_[0] + (mnx - off_x_) * ele_size_;
     t.transform[5] = length_pixel_ * (1 << level); t.transform[7] = min_[1] + (mny - off_y_) * ele_size_;
     t.transform[10] = 1; t.transform[15] = 1;
+    std::memcpy(t.plane7, plane_.t, 24); std::memcpy(t.plane7 + 3, plane_.q, 32);
     if (t.kind == SaveTarget::Extent) return true;
-    const bool file = t.kind == SaveTarget::File;
+    const bool file = t.kind == SaveTarget::File, web = t.kind == SaveTarget::Tiles;
+    if (web && (single_band_ || !t.web)) { set_error("save: map tiles of a mosaic in HBM were asked for where there is none"); return false; }
     if (file && single_band_) { set_error("save: the stream of a mosaic in HBM was asked for where there is none"); return false; }
     if (file && t.route == SaveRoute::DeviceJpeg && !jpeg_size_ok("save", t.rows, t.cols)) return false;          // before anything is made: no file
     const size_t out_bytes = (size_t)t.rows * t.cols * 3, mask_bytes = (size_t)t.rows * t.cols;
@@ -2019,12 +2023,23 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
         launch_save_level(stream_, lay_, level, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
         prof_end();
         HIP_OK(hipGetLastError());
-    } else if (file || bgr) {
+    } else if (file || bgr || web) {
         double P = 0; for (int i = 0; i <= L; i++) P += 1.0 / (double)(1 << (2 * i));
         prof_begin(K_SAVE_FUSED, (double)cnt * kElePixels * kElePixels * (P * px + 4) + (double)out_bytes);
         launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
         prof_end();
         HIP_OK(hipGetLastError());
+    }
+    if (web) {          // sampled from the mosaic and the coverage of the same table where both lie; streams, masks and flags cross to the host
+        if (!cover_plane_.reserve(mask_bytes / 8) || !cover_bytes_.reserve(mask_bytes)) return false;
+        launch_coverage_tiles(stream_, (const uint64_t*)mosaic_table_.p, wx, wy, lay_.w_off[0], (uint8_t*)cover_plane_.p, nullptr, nullptr);
+        launch_coverage_expand(stream_, (const uint8_t*)cover_plane_.p, t.rows, t.cols, (uint8_t*)cover_bytes_.p);
+        HIP_OK(hipGetLastError());
+        double px2ll[6];
+        webtiles::georef_compose(t.transform, t.plane7, t.web->gps_origin, px2ll);
+        if (t.web->report) { std::memcpy(t.web->report, px2ll, sizeof px2ll); t.web->report[6] = t.rows; t.web->report[7] = t.cols; }
+        return webtiles_export(blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, cover_bytes_.p, (size_t)t.cols, px2ll, t.web->zmin, t.web->zmax, t.web->quality, opt_.bg_color,
+                               t.web->want_pixels, t.web->sink, t.web->user, jpeg_enc_, stream_);
     }
     if (!file) {
         std::vector<OutPiece> pieces;
@@ -2069,6 +2084,46 @@ bool FusionMap::save_to_memory_level(int level, uint8_t* bgr, int* rows, int* co
     if (!save_mosaic(t)) return false;
     *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
     return true;
+}
+
+bool FusionMap::webtiles_georef(const double gps_origin[3], double px2ll[6], int* rows, int* cols)
+{
+    if (opt_.shard_count > 1) { set_error("pf_webtiles: a sharded map (shard_count > 1) holds a part of the mosaic only: gather it (pf_dist_save_to_memory) and use pf_webtiles_device"); return false; }
+    SaveTarget t;
+    if (!save_mosaic(t)) { set_error("pf_webtiles: the map has no content"); return false; }
+    double p[6], A[4];
+    webtiles::georef_compose(t.transform, t.plane7, gps_origin, p);
+    if (!webtiles::invert2(p, A)) { set_error(std::string("pf_webtiles: ") + webtiles::plan_message(webtiles::kPlanSingular)); return false; }
+    std::memcpy(px2ll, p, sizeof p);
+    if (rows) *rows = t.rows;
+    if (cols) *cols = t.cols;
+    return true;
+}
+
+bool FusionMap::webtiles(const WebTilesJob& job)
+{
+    if (opt_.shard_count > 1) { set_error("pf_webtiles: a sharded map (shard_count > 1) holds a part of the mosaic only: gather it (pf_dist_save_to_memory) and use pf_webtiles_device"); return false; }
+    SaveTarget t;
+    if (!single_band_) {
+        t.kind = SaveTarget::Tiles; t.web = &job;
+        if (save_mosaic(t)) return true;
+        if (!t.found) set_error("pf_webtiles: the map has no content");
+        return false;
+    }
+    // Map2DCPU semantics: the host mosaic and its alpha mask of one moment, uploaded, through the same device path
+    std::vector<uint8_t> img, cover;
+    t.kind = SaveTarget::Image; t.image = &img; t.mask_image = &cover;
+    if (!save_mosaic(t)) { set_error("pf_webtiles: the map has no content"); return false; }
+    double px2ll[6];
+    webtiles::georef_compose(t.transform, t.plane7, job.gps_origin, px2ll);
+    if (job.report) { std::memcpy(job.report, px2ll, sizeof px2ll); job.report[6] = t.rows; job.report[7] = t.cols; }
+    std::lock_guard<std::mutex> l(mu_);
+    if (!set_device()) return false;
+    if (!blend_out_bgr_.reserve(img.size()) || !cover_bytes_.reserve(cover.size())) return false;
+    HIP_OK(hipMemcpy(blend_out_bgr_.p, img.data(), img.size(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(cover_bytes_.p, cover.data(), cover.size(), hipMemcpyHostToDevice));
+    return webtiles_export(blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, cover_bytes_.p, (size_t)t.cols, px2ll, job.zmin, job.zmax, job.quality, opt_.bg_color,
+                           job.want_pixels, job.sink, job.user, jpeg_enc_, stream_);
 }
 
 bool FusionMap::save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign, bool masked)

@@ -10,6 +10,7 @@
 #include "image_io.hpp"
 #include "jpeg_encode.hpp"
 #include "tiff_pyramid.hpp"
+#include "webtiles.hpp"
 #include <hip/hip_runtime.h>
 #include <condition_variable>
 #include <cstdlib>
@@ -114,14 +115,19 @@ public:
     bool save_tiff(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff); }
     // save_tiff() with a transparency mask behind every image (pf_save_tiff_masked): covered = the level-0 weight is not 0
     bool save_tiff_masked(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff, nullptr, true); }
+    // pf_webtiles: what the tiles are made for and where they go
+    struct WebTilesJob { const double* gps_origin; int zmin, zmax, quality; bool want_pixels; pf_webtile_sink sink; void* user;
+                         double* report; };          // report (may be null): px2ll[6], rows, cols of the mosaic the tiles are made from
     struct ForeignTile { int ix, iy; const void* dev; };          // a tile slot image held outside the store (gathered for save)
     // Where the collapsed mosaic of one save goes.  A value: what the caller asks for, and what save_mosaic() found out on the way
     struct SaveTarget {
         enum Kind { Extent,      // nowhere: rows, cols and the origin tile alone (the first call of pf_save_to_memory)
                     Buffer,      // bgr: the caller's rows * cols * 3 bytes, sized from an earlier Extent call (its second call)
                     Image,       // image: the library's own, sized inside the call from the extent the pixels are made for
-                    File };      // a file made on the GPU from the mosaic where it lies in HBM: name, route (a device route), quality, force_bigtiff
+                    File,        // a file made on the GPU from the mosaic where it lies in HBM: name, route (a device route), quality, force_bigtiff
+                    Tiles };     // Web-Mercator map tiles made on the GPU from the mosaic and its coverage where they lie (webtiles.hpp): web
         Kind kind = Extent;
+        const WebTilesJob* web = nullptr;
         uint8_t* bgr = nullptr;
         std::vector<uint8_t>* image = nullptr;
         const char* name = nullptr; SaveRoute route = SaveRoute::HostImage; int quality = 95; bool force_bigtiff = false;
@@ -132,8 +138,10 @@ public:
         bool masked = false;
         int level = 0;                  // Extent / Buffer without mask only: the mosaic collapsed down to this pyramid level, (256 >> level)^2 pixels a tile
         // results
+        bool found = false;             // the map is prepared and holds content: whatever failed after that has said why
         int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
         double transform[16] = {};      // the ModelTransformationTag of a TIFF of this mosaic: pixel -> plane metres
+        double plane7[7] = {};          // the plane's pose of the same moment: plane metres -> world
     };
     // ONE pass under mu_: drains, takes the extent, collapses the mosaic and hands it to the target.  foreign: tiles of other ranks
     // that take part without entering the store (dist.cpp)
@@ -146,6 +154,10 @@ public:
     bool save_to_memory_mask(uint8_t* bgr, uint8_t* mask, int* rows, int* cols, int* tx0, int* ty0);
     // ... of the view of pyramid level `level` (pf_save_to_memory_level)
     bool save_to_memory_level(int level, uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0);
+    // pf_webtiles_georef / pf_webtiles (webtiles_plan.hpp, webtiles.hpp): the mosaic of save_to_memory on the globe, and as map tiles.  A
+    // multi-band map's tiles are one more device route of save_mosaic(); a single-band map's host mosaic and alpha mask are uploaded
+    bool webtiles_georef(const double gps_origin[3], double px2ll[6], int* rows, int* cols);
+    bool webtiles(const WebTilesJob& job);
 
     // seam exchange support (dist.cpp)
     using TileRec = pf::TileRec;        // dist_plan.hpp
