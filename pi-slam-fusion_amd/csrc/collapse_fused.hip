@@ -31,8 +31,6 @@ namespace {
 
 using namespace cf;
 
-constexpr int kBW = 128, kBH = 32;                    // level-0 block of a workgroup
-constexpr int kCT = 256;                              // threads
 #ifndef PF_CF_WAVES
 #define PF_CF_WAVES 5
 #endif
@@ -40,46 +38,18 @@ constexpr int kCT = 256;                              // threads
 #define PF_CF_ABLATE 0
 #endif
 constexpr int kCFWaves = PF_CF_WAVES;                 // waves per SIMD the register budget is cut for (5: 96 VGPRs, five workgroups per CU; 6 spilled and was 30 % slower, profiles/r06_blend_ab.md)
-constexpr int region_edge(int s, int level) { for (int i = 0; i < level; i++) s = ((s + 1) >> 1) + 2; return s; }
-constexpr int region_px(int level) { return region_edge(kBW, level) * region_edge(kBH, level); }
-constexpr int region_px_total(int from) { int n = 0; for (int i = from; i < kMaxLevels; i++) n += region_px(i); return n; }
-constexpr int kLdsPx = region_px_total(1);            // 1925 pixels = 23 100 B of 3 x 4-byte components
-static_assert(region_edge(128, 1) == 66 && region_edge(32, 1) == 18 && region_edge(66, 1) == 35, "pyrUp dependence regions");
 
 typedef float    f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u3 __attribute__((ext_vector_type(3), aligned(4)));
 
-// region of a level held in LDS: rows [y0, y0 + h) x cols [x0, x0 + w) of the level's image (rows x cols); the regions of levels
-// 1, 2, ... lie back to back, pixel p of the flat list at lds[3 p]
-struct Reg {
-    int y0, x0, h, w;
-    int poff, rows, cols;                // first pixel in the flat list; extent of the level's image
-};
-// what the flat loader needs of it, per level, in LDS
+// what the flat loader needs of a level's region (cf::Reg), per level, in LDS
 struct RegL { int poff, y0, x0, w; float rcp_w; int lap_off, pad0_, pad1_; };
 
 struct Shared {
     RegL reg[kMaxLevels];
     BlendJob job;
 };
-
-// the recurrence above from the level-0 block; every input is workgroup-uniform, so this is scalar code
-__device__ __forceinline__ Reg level_region(int level, int Y0, int X0, int rows0, int cols0)
-{
-    int ylo = Y0, yhi = Y0 + kBH - 1, xlo = X0, xhi = X0 + kBW - 1, poff = 0;
-    Reg r{};
-    for (int i = 1; i <= level; i++) {
-        const int rows = rows0 >> i, cols = cols0 >> i;
-        ylo = (ylo - 1) >> 1; if (ylo < 0) ylo = 0;
-        xlo = (xlo - 1) >> 1; if (xlo < 0) xlo = 0;
-        yhi = (yhi >> 1) + 1; if (yhi > rows - 1) yhi = rows - 1;
-        xhi = (xhi >> 1) + 1; if (xhi > cols - 1) xhi = cols - 1;
-        r.y0 = ylo; r.x0 = xlo; r.h = yhi - ylo + 1; r.w = xhi - xlo + 1; r.poff = poff; r.rows = rows; r.cols = cols;
-        poff += r.h * r.w;
-    }
-    return r;
-}
 
 // 4 consecutive level-0 pixels of a row (12 components): loads and stores by the widest aligned pieces
 template <bool F32> struct Row4;
@@ -162,12 +132,12 @@ __global__ __launch_bounds__(kCT, kCFWaves) void k_collapse_fused(TileLayout lay
 
     // ---- regions of levels 1..L this block depends on (thread i: level i, for the flat loader)
     if (tid >= 1 && tid <= L) {
-        const Reg r = level_region(tid, Y0, X0, rows0, cols0);
+        const Reg r = level_region(0, tid, Y0, X0, kBH, kBW, rows0, cols0);
         RegL q; q.poff = r.poff; q.y0 = r.y0; q.x0 = r.x0; q.w = r.w; q.rcp_w = 1.f / (float)r.w; q.lap_off = (int)lay.lap_off[tid]; q.pad0_ = q.pad1_ = 0;
         sh.reg[tid] = q;
     }
-    const Reg r1 = L >= 1 ? level_region(1, Y0, X0, rows0, cols0) : Reg{};
-    const Reg rL = L >= 1 ? level_region(L, Y0, X0, rows0, cols0) : Reg{};
+    const Reg r1 = L >= 1 ? level_region(0, 1, Y0, X0, kBH, kBW, rows0, cols0) : Reg{};
+    const Reg rL = L >= 1 ? level_region(0, L, Y0, X0, kBH, kBW, rows0, cols0) : Reg{};
     const int total = L >= 1 ? rL.poff + rL.h * rL.w : 0;
     __syncthreads();
 
@@ -236,63 +206,8 @@ __global__ __launch_bounds__(kCT, kCFWaves) void k_collapse_fused(TileLayout lay
     }
     __syncthreads();
 
-    // ---- 2. restore levels L-1 .. 1 in place: pyr[i-1] = pyrUp(pyr[i]) + pyr[i-1], one thread per 2 x 2 destination quad
-    // (quads aligned to even coordinates; a quad on the rim of the region has pixels outside it, which are not stored)
-    for (int i = (PF_CF_ABLATE & 2) ? 1 : L; i >= 2; i--) {
-        const Reg rs = level_region(i, Y0, X0, rows0, cols0), rd = level_region(i - 1, Y0, X0, rows0, cols0);
-        const WT* src = lds + rs.poff * 3 - (rs.y0 * rs.w + rs.x0) * 3;          // [(y * w + x) * 3] = source pixel (y, x)
-        WT* dst = lds + rd.poff * 3 - (rd.y0 * rd.w + rd.x0) * 3;
-        const int qy0 = rd.y0 >> 1, qx0 = rd.x0 >> 1, qw = ((rd.x0 + rd.w - 1) >> 1) - qx0 + 1, nq = (((rd.y0 + rd.h - 1) >> 1) - qy0 + 1) * qw;
-        const float rcp_qw = 1.f / (float)qw;
-        const int ylo = rs.y0, yhi = rs.y0 + rs.h - 1, xlo = rs.x0, xhi = rs.x0 + rs.w - 1;
-        for (int qi = rt; qi < nq; qi += kCT) {
-            const int qy = div_small(qi, rcp_qw), qx = qi - qy * qw;
-            const int sy = qy0 + qy, sx = qx0 + qx;
-            // source rows sy - 1, sy, sy + 1 with pyrUp's row rule (-1 -> 1, rows -> rows - 1), then clamped into the region: a row the region
-            // lacks is only ever asked for by a destination pixel outside the destination region
-            int r0 = sy - 1; if (r0 < 0) r0 = rs.rows > 1 ? 1 : 0;
-            int r2 = sy + 1; if (r2 > rs.rows - 1) r2 = rs.rows - 1;
-            r0 = r0 < ylo ? ylo : (r0 > yhi ? yhi : r0); r2 = r2 > yhi ? yhi : r2;
-            const int r1y = sy > yhi ? yhi : sy;
-            int ca = sx - 1; ca = ca < xlo ? xlo : ca;
-            int cc = sx + 1; cc = cc > xhi ? xhi : cc;
-            const int cb = sx > xhi ? xhi : sx;
-            const int rowo[3] = { r0 * rs.w * 3, r1y * rs.w * 3, r2 * rs.w * 3 };
-            WT E[3][3], O[3][3];
-            if (sx > 0 && sx < rs.cols - 1) {
-#pragma unroll
-                for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        const WT a = src[rowo[rr] + ca * 3 + k], b = src[rowo[rr] + cb * 3 + k], c = src[rowo[rr] + cc * 3 + k];
-                        E[rr][k] = a + b * 6 + c; O[rr][k] = b + c;
-                    }
-            } else {
-                const bool single = rs.cols == 1, left = sx == 0;
-#pragma unroll
-                for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        const WT a = src[rowo[rr] + ca * 3 + k], b = src[rowo[rr] + cb * 3 + k], c = src[rowo[rr] + cc * 3 + k];
-                        if (single)    { E[rr][k] = b * 8; O[rr][k] = b * 2; }
-                        else if (left) { E[rr][k] = b * 6 + c * 2; O[rr][k] = b + c; }
-                        else           { E[rr][k] = a + b * 7; O[rr][k] = b * 2; }      // right edge
-                    }
-            }
-            const int y = 2 * sy, x = 2 * sx;
-            const bool vy0 = y >= rd.y0, vy1 = y + 1 < rd.y0 + rd.h, vx0 = x >= rd.x0, vx1 = x + 1 < rd.x0 + rd.w;
-            WT* d0 = dst + (y * rd.w + x) * 3;
-            WT* d1 = d0 + rd.w * 3;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                if (vy0 && vx0) d0[k] = add_sat(up_ee(E[0][k], E[1][k], E[2][k]), d0[k]);
-                if (vy0 && vx1) d0[3 + k] = add_sat(up_eo(O[0][k], O[1][k], O[2][k]), d0[3 + k]);
-                if (vy1 && vx0) d1[k] = add_sat(up_oe(E[1][k], E[2][k]), d1[k]);
-                if (vy1 && vx1) d1[3 + k] = add_sat(up_oo(O[1][k], O[2][k]), d1[3 + k]);
-            }
-        }
-        __syncthreads();
-    }
+    // ---- 2. restore levels L-1 .. 1 in place (collapse_common.hpp)
+    restore_levels<WT, kCT>(lds, 0, (PF_CF_ABLATE & 2) ? 1 : L, Y0, X0, kBH, kBW, rows0, cols0, rt);
 
     // ---- 3. level 0: 2 rows x 4 columns per thread
     const PF_GLOBAL T* lap0 = (const PF_GLOBAL T*)(self + lay.lap_off[0]);
@@ -358,13 +273,10 @@ __global__ __launch_bounds__(kCT, kCFWaves) void k_collapse_fused(TileLayout lay
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
                     const int e = p * 3 + k;
-                    if constexpr (MOSAIC) {
-                        if constexpr (F32) b8[e] = zero ? sat_u8(bg) : sat_u8(__float2int_rn(px[r].v[e] * 255.f));
-                        else b8[e] = zero ? sat_u8(bg) : sat_u8(px[r].v[e]);
-                    } else {
+                    if constexpr (MOSAIC) b8[e] = zero ? sat_u8(bg) : view_8u<F32>(px[r].v[e]);
+                    else {
                         if (zero) px[r].v[e] = (WT)0;
-                        if constexpr (F32) b8[e] = sat_u8(__float2int_rn(px[r].v[e] * 255.f));
-                        else b8[e] = sat_u8(px[r].v[e]);
+                        b8[e] = view_8u<F32>(px[r].v[e]);
                     }
                 }
             }

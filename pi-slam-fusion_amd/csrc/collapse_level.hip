@@ -9,8 +9,8 @@
 //   tile views (MOSAIC = false): the block is clipped to the tile, E_k x E_k.  4 blocks a tile at k = 1, 2 at k = 2, and from
 //     k = 3 on (E_k <= 32) one workgroup takes a whole tile;
 //   mosaic view (MOSAIC = true): the block grid covers the wy E_k x wx E_k image, the last row / column of blocks clipped to it.
-//   1. the regions of levels k+1 .. L the block depends on (one pixel of halo per level: collapse_fused.hip's recurrence started at
-//      level k) go from the tile slots straight into LDS -- at most the 1925 pixels = 23 100 B of the level-0 kernel;
+//   1. the regions of levels k+1 .. L the block depends on (one pixel of halo per level: cf::level_region, the recurrence
+//      started at level k) go from the tile slots straight into LDS -- at most the 1925 pixels = 23 100 B of the level-0 kernel;
 //   2. levels L-1 .. k+1 are restored in place, one thread per 2 x 2 destination quad, with pyrUp_'s edge forms at the borders of
 //      the padded square / the mosaic;
 //   3. level k: a thread takes a 2 x 2 quad, forms pyrUp of level k+1 from LDS, adds the tile's own level-k Laplacian, masks by
@@ -18,6 +18,7 @@
 //      pyrUp: the masked top level, pixel by pixel.
 // Nothing of a level > k returns to HBM, level k is read once and the result written once.
 //
+// Phase 2 and every sum are collapse_common.hpp's, shared with collapse_fused.hip; this file is the simple loads (1) and the 2 x 2 emit (3).
 // Bit-exactness: -ffp-contract=off and the sums of collapse_common.hpp, in the association order of OpenCV 2.4.9's pyrUp_.
 #include "collapse_common.hpp"
 
@@ -25,73 +26,6 @@ namespace pf {
 namespace {
 
 using namespace cf;
-
-constexpr int kBW = 128, kBH = 32;                    // largest level-k block of a workgroup
-constexpr int kCT = 256;                              // threads
-constexpr int region_edge(int s, int up) { for (int i = 0; i < up; i++) s = ((s + 1) >> 1) + 2; return s; }
-constexpr int region_px_total() { int n = 0; for (int i = 1; i < kMaxLevels; i++) n += region_edge(kBW, i) * region_edge(kBH, i); return n; }
-constexpr int kLdsPx = region_px_total();             // 1925 pixels: the regions of a full block with k + 8 levels above it
-static_assert(kLdsPx == 1925 && kBW * kBH <= 4096 && kBW <= 128, "div_small: idx < 4096, w <= 128");
-
-// region of a level held in LDS: rows [y0, y0 + h) x cols [x0, x0 + w) of the level's image (rows x cols); the regions of levels
-// k+1, k+2, ... lie back to back, pixel p of the flat list at lds[3 p]
-struct Reg {
-    int y0, x0, h, w;
-    int poff, rows, cols;
-};
-
-// what the level-k block rows [Y0, Y0 + bh) x cols [X0, X0 + bw) needs of level `level` > k: pyrUp is a 3-tap filter, so rows
-// [lo, hi] of level i-1 need rows [(lo-1)>>1, (hi>>1)+1] of level i.  rowsk x colsk: the level-k image.  Workgroup-uniform.
-__device__ __forceinline__ Reg level_region(int k, int level, int Y0, int X0, int bh, int bw, int rowsk, int colsk)
-{
-    int ylo = Y0, yhi = Y0 + bh - 1, xlo = X0, xhi = X0 + bw - 1, poff = 0;
-    Reg r{};
-    for (int i = k + 1; i <= level; i++) {
-        const int rows = rowsk >> (i - k), cols = colsk >> (i - k);
-        ylo = (ylo - 1) >> 1; if (ylo < 0) ylo = 0;
-        xlo = (xlo - 1) >> 1; if (xlo < 0) xlo = 0;
-        yhi = (yhi >> 1) + 1; if (yhi > rows - 1) yhi = rows - 1;
-        xhi = (xhi >> 1) + 1; if (xhi > cols - 1) xhi = cols - 1;
-        r.y0 = ylo; r.x0 = xlo; r.h = yhi - ylo + 1; r.w = xhi - xlo + 1; r.poff = poff; r.rows = rows; r.cols = cols;
-        poff += r.h * r.w;
-    }
-    return r;
-}
-
-// pyrUp_'s horizontal sums for the 2 x 2 destination quad under source pixel (sy, sx) of the level whose region rs lies at `src`
-// ([(y * w + x) * 3] = source pixel (y, x)): E = even-column sum, O = odd-column sum / 4, for source rows sy-1 / sy / sy+1 under
-// pyrUp's row rule (-1 -> 1, rows -> rows - 1).  Rows and columns are clamped into the region: one the region lacks is only ever
-// asked for by a destination pixel outside the destination region, which is not stored.
-template <class WT>
-__device__ __forceinline__ void quad_sums(const WT* src, const Reg& rs, int sy, int sx, WT E[3][3], WT O[3][3])
-{
-    const int ylo = rs.y0, yhi = rs.y0 + rs.h - 1, xlo = rs.x0, xhi = rs.x0 + rs.w - 1;
-    int r0 = sy - 1; if (r0 < 0) r0 = rs.rows > 1 ? 1 : 0;
-    int r2 = sy + 1; if (r2 > rs.rows - 1) r2 = rs.rows - 1;
-    r0 = r0 < ylo ? ylo : (r0 > yhi ? yhi : r0); r2 = r2 > yhi ? yhi : r2;
-    const int r1 = sy > yhi ? yhi : sy;
-    int ca = sx - 1; ca = ca < xlo ? xlo : ca;
-    int cc = sx + 1; cc = cc > xhi ? xhi : cc;
-    const int cb = sx > xhi ? xhi : sx;
-    const int rowo[3] = { r0 * rs.w * 3, r1 * rs.w * 3, r2 * rs.w * 3 };
-    const bool inner = sx > 0 && sx < rs.cols - 1, single = rs.cols == 1, left = sx == 0;
-#pragma unroll
-    for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const WT a = src[rowo[rr] + ca * 3 + c], b = src[rowo[rr] + cb * 3 + c], d = src[rowo[rr] + cc * 3 + c];
-            if (inner)       { E[rr][c] = a + b * 6 + d; O[rr][c] = b + d; }
-            else if (single) { E[rr][c] = b * 8; O[rr][c] = b * 2; }
-            else if (left)   { E[rr][c] = b * 6 + d * 2; O[rr][c] = b + d; }
-            else             { E[rr][c] = a + b * 7; O[rr][c] = b * 2; }      // right edge
-        }
-}
-
-template <bool F32> __device__ __forceinline__ uint32_t view_8u(typename Px<F32>::WT v)
-{
-    if constexpr (F32) return sat_u8(__float2int_rn(v * 255.f));
-    else return sat_u8(v);
-}
 
 // One workgroup = one block of a level-k result (k >= 1; see the header).
 //   MOSAIC = false: block (blockIdx % per_tile) of tile job[blockIdx / per_tile]; results to raw / bgr at tile index job.out
@@ -144,33 +78,8 @@ __global__ __launch_bounds__(kCT) void k_collapse_level(TileLayout lay, int k, c
     }
     __syncthreads();
 
-    // ---- 2. restore levels L-1 .. k+1 in place: pyr[i-1] = pyrUp(pyr[i]) + pyr[i-1], one thread per 2 x 2 destination quad
-    // (quads aligned to even coordinates; a quad on the rim of the region has pixels outside it, which are not stored)
-    for (int i = L; i >= k + 2; i--) {
-        const Reg rs = level_region(k, i, Y0, X0, bh, bw, rowsk, colsk), rd = level_region(k, i - 1, Y0, X0, bh, bw, rowsk, colsk);
-        const WT* src = lds + rs.poff * 3 - (rs.y0 * rs.w + rs.x0) * 3;
-        WT* dst = lds + rd.poff * 3 - (rd.y0 * rd.w + rd.x0) * 3;
-        const int qy0 = rd.y0 >> 1, qx0 = rd.x0 >> 1, qw = ((rd.x0 + rd.w - 1) >> 1) - qx0 + 1, nq = (((rd.y0 + rd.h - 1) >> 1) - qy0 + 1) * qw;
-        const float rcp_qw = 1.f / (float)qw;
-        for (int qi = tid; qi < nq; qi += kCT) {
-            const int qy = div_small(qi, rcp_qw), qx = qi - qy * qw;
-            const int sy = qy0 + qy, sx = qx0 + qx;
-            WT Es[3][3], Os[3][3];
-            quad_sums<WT>(src, rs, sy, sx, Es, Os);
-            const int y = 2 * sy, x = 2 * sx;
-            const bool vy0 = y >= rd.y0, vy1 = y + 1 < rd.y0 + rd.h, vx0 = x >= rd.x0, vx1 = x + 1 < rd.x0 + rd.w;
-            WT* d0 = dst + (y * rd.w + x) * 3;
-            WT* d1 = d0 + rd.w * 3;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                if (vy0 && vx0) d0[c] = add_sat(up_ee(Es[0][c], Es[1][c], Es[2][c]), d0[c]);
-                if (vy0 && vx1) d0[3 + c] = add_sat(up_eo(Os[0][c], Os[1][c], Os[2][c]), d0[3 + c]);
-                if (vy1 && vx0) d1[c] = add_sat(up_oe(Es[1][c], Es[2][c]), d1[c]);
-                if (vy1 && vx1) d1[3 + c] = add_sat(up_oo(Os[1][c], Os[2][c]), d1[3 + c]);
-            }
-        }
-        __syncthreads();
-    }
+    // ---- 2. restore levels L-1 .. k+1 in place (collapse_common.hpp)
+    restore_levels<WT, kCT>(lds, k, L, Y0, X0, bh, bw, rowsk, colsk, tid);
 
     // ---- 3. level k.  A pixel's own Laplacian and weight: (ty, tx) inside the tile at `tile` (0: no tile there, mosaic only)
     const uint32_t lapk = lay.lap_off[k], wk = lay.w_off[k];
@@ -232,8 +141,8 @@ __global__ __launch_bounds__(kCT) void k_collapse_level(TileLayout lay, int k, c
         place(y, x, tile, ty, tx, o);
         WT up[4][3];
         if (tile) {
-            WT Es[3][3], Os[3][3];
-            quad_sums<WT>(src1, r1, y >> 1, x >> 1, Es, Os);
+            const QuadSums<WT> q = quad_sums<WT>(src1, r1, y >> 1, x >> 1);
+            const auto& Es = q.E; const auto& Os = q.O;
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 up[0][c] = up_ee(Es[0][c], Es[1][c], Es[2][c]);

@@ -1624,6 +1624,24 @@ bool FusionMap::download(const std::vector<OutPiece>& pieces)
 // bytes alone).  One launch of the fused collapse kernel per kBlendLaunch tiles, "blend with neighbours" and "blend by self"
 // tiles side by side in it; the pixels come back through download().  level > 0: the view of that pyramid level (collapse_level.hip),
 // E x E pixels a tile with E = 256 >> level; no halo strips and no JPEG streams there.
+// The nine sources of Ele::blend's 3 x 3 assembly for tile (ix, iy) (.cpp:93-117; row-major, [4] = the tile itself): a neighbour comes
+// from the store, otherwise from its packed halo strip set (halo: nullptr or the tile's 9 device pointers; bit j of strips), otherwise
+// there are "no neighbours": false, and the tile is blended by itself (.cpp:131-145).  hq: HighQualityShow
+static bool blend_sources(TileStore& store, bool hq, int ix, int iy, const void* const* halo, const void* src[9], unsigned& strips)
+{
+    strips = 0;
+    if (!hq) return false;
+    for (int dy = -1; dy <= 1; dy++)
+        for (int dx = -1; dx <= 1; dx++) {
+            const int j = 3 * (dy + 1) + dx + 1;
+            Tile* n = store.find(ix + dx, iy + dy);
+            if (n && !n->fresh) src[j] = n->base;
+            else if (halo && halo[j]) { src[j] = halo[j]; strips |= 1u << j; }
+            else return false;
+        }
+    return true;
+}
+
 bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg, int level)
 {
     Section sec(this, T_UPDATE_TEXTURE);
@@ -1661,17 +1679,9 @@ bool FusionMap::blend_batch(const std::vector<std::pair<int, int>>& tiles, const
         for (size_t t = c0; t < c0 + cn; t++) {
             Tile* self = store_.find(tiles[t].first, tiles[t].second);
             if (!self || self->fresh) continue;
-            const void* const* halo = halo9 ? halo9 + 9 * t : nullptr;
-            BlendJob jb{}; bool all = opt_.high_quality_show != 0;
-            for (int dy = -1; dy <= 1 && all; dy++)
-                for (int dx = -1; dx <= 1; dx++) {
-                    const int j = 3 * (dy + 1) + dx + 1;
-                    Tile* n = store_.find(tiles[t].first + dx, tiles[t].second + dy);
-                    if (n && !n->fresh) jb.src[j] = (uint64_t)(uintptr_t)n->base;
-                    else if (halo && halo[j]) { jb.src[j] = (uint64_t)(uintptr_t)halo[j]; jb.strip_mask |= 1u << j; }
-                    else { all = false; break; }
-                }
-            if (!all) { for (auto& q : jb.src) q = 0; jb.strip_mask = 0; }
+            BlendJob jb{}; const void* src[9]; unsigned strips;
+            const bool all = blend_sources(store_, opt_.high_quality_show != 0, tiles[t].first, tiles[t].second, halo9 ? halo9 + 9 * t : nullptr, src, strips);
+            if (all) { for (int j = 0; j < 9; j++) jb.src[j] = (uint64_t)(uintptr_t)src[j]; jb.strip_mask = strips; }
             jb.src[4] = (uint64_t)(uintptr_t)self->base;
             jb.border = all ? 1 : 0; jb.out = (int)(t - c0);
             jobs.push_back(jb);
@@ -1748,18 +1758,11 @@ bool FusionMap::blend_batch_per_level(const std::vector<std::pair<int, int>>& ti
             for (size_t t = c0; t < c0 + cn; t++) {
                 Tile* self = store_.find(tiles[t].first, tiles[t].second);
                 if (!self || self->fresh) continue;
-                const void* const* halo = halo9 ? halo9 + 9 * t : nullptr;
-                BlendSrc nb[9]; bool all = opt_.high_quality_show != 0;
-                for (int dy = -1; dy <= 1 && all; dy++)
-                    for (int dx = -1; dx <= 1; dx++) {
-                        const int j = 3 * (dy + 1) + dx + 1;
-                        Tile* n = store_.find(tiles[t].first + dx, tiles[t].second + dy);
-                        if (n && !n->fresh) nb[j] = { n->base, 0 };
-                        else if (halo && halo[j]) nb[j] = { halo[j], 1 };
-                        else { all = false; break; }
-                    }
+                BlendSrc nb[9] = {}; const void* src[9]; unsigned strips;
+                const bool all = blend_sources(store_, opt_.high_quality_show != 0, tiles[t].first, tiles[t].second, halo9 ? halo9 + 9 * t : nullptr, src, strips);
                 if ((all ? 0 : 1) != mode) continue;
-                if (!all) { for (auto& q : nb) q = { nullptr, 0 }; nb[4] = { self->base, 0 }; }
+                if (all) for (int j = 0; j < 9; j++) nb[j] = { src[j], (int)((strips >> j) & 1u) };
+                else nb[4] = { self->base, 0 };
                 srcs.insert(srcs.end(), nb, nb + 9);
                 idx.push_back((int)(t - c0));
                 present[t - c0] = 1;
@@ -1837,16 +1840,7 @@ bool FusionMap::blend_tile(int ix, int iy, void* raw, uint8_t* bgr, const void* 
     return blend_batch(one, halo, raw, bgr);
 }
 
-bool FusionMap::blend_list(const std::vector<std::pair<int, int>>& tiles, uint8_t* bgr)
-{
-    if (single_band_) {          // the Map2DCPU tile is displayable as is (see blend_tile): a tile that does not exist keeps the buffer's bytes
-        for (size_t i = 0; i < tiles.size(); i++) (void)blend_tile(tiles[i].first, tiles[i].second, nullptr, bgr + i * (size_t)kElePixels * kElePixels * 3, nullptr);
-        return init_ok_;
-    }
-    std::lock_guard<std::mutex> l(mu_); (void)drain();
-    if (!init_ok_ || !set_device()) return false;
-    return blend_batch(tiles, nullptr, nullptr, bgr);
-}
+bool FusionMap::blend_list(const std::vector<std::pair<int, int>>& tiles, uint8_t* bgr) { return blend_list_level(tiles, 0, bgr, nullptr); }
 
 // The views of pyramid level `level` (pf_blend_tiles_level, pf_blend_changed_level, pf_save_to_memory_level): which levels a map has
 bool FusionMap::level_ok(const char* who, int level)
@@ -1861,11 +1855,11 @@ bool FusionMap::level_ok(const char* who, int level)
     return true;
 }
 
-// pf_blend_tiles_level: blend_list with the 8U and / or the raw view, at any level.  Level 0 is blend_list's own path
+// pf_blend_tiles_level: the 8U and / or the raw view of the tiles, at any level.  blend_list (pf_blend_tiles) is its level 0, 8U only
 bool FusionMap::blend_list_level(const std::vector<std::pair<int, int>>& tiles, int level, uint8_t* bgr, void* raw)
 {
     if (!level_ok("pf_blend_tiles_level", level)) return false;
-    if (single_band_) {          // level 0: the tile as it is (see blend_tile); raw is its four bytes a pixel
+    if (single_band_) {          // level 0: the Map2DCPU tile is displayable as is (see blend_tile), raw is its four bytes a pixel; a tile that does not exist keeps the buffer's bytes
         const size_t n = (size_t)kElePixels * kElePixels;
         for (size_t i = 0; i < tiles.size(); i++)
             (void)blend_tile(tiles[i].first, tiles[i].second, raw ? (char*)raw + i * n * 4 : nullptr, bgr ? bgr + i * n * 3 : nullptr, nullptr);
@@ -2015,40 +2009,31 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
         return true;
     }
 #endif
-    // one launch: paste, collapse in LDS, 8U, background (collapse_fused.hip).  Algorithmic bytes: every tile's Laplacians and
-    // level-0 weights read once, the mosaic written once.
-    if (level > 0) {          // the same from level `level` down (collapse_level.hip): levels level .. L and that level's weights read
+    // one launch: paste, collapse in LDS from level `level` down, 8U, background (level 0: collapse_fused.hip, above: collapse_level.hip).
+    // Algorithmic bytes: every tile's Laplacians of levels level .. L and that level's weights read once, the mosaic written once.
+    // A request for the mask alone (Buffer without bgr) needs no pixels
+    if (file || bgr || web) {
         double P = 0; for (int i = level; i <= L; i++) P += 1.0 / (double)(1 << (2 * i));
-        prof_begin(K_SAVE_LEVEL, (double)cnt * kElePixels * kElePixels * (P * px + 4.0 / (double)(1 << (2 * level))) + (double)out_bytes);
-        launch_save_level(stream_, lay_, level, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
-        prof_end();
-        HIP_OK(hipGetLastError());
-    } else if (file || bgr || web) {
-        double P = 0; for (int i = 0; i <= L; i++) P += 1.0 / (double)(1 << (2 * i));
-        prof_begin(K_SAVE_FUSED, (double)cnt * kElePixels * kElePixels * (P * px + 4) + (double)out_bytes);
-        launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
+        prof_begin(level ? K_SAVE_LEVEL : K_SAVE_FUSED, (double)cnt * kElePixels * kElePixels * (P * px + 4.0 / (double)(1 << (2 * level))) + (double)out_bytes);
+        if (level) launch_save_level(stream_, lay_, level, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
+        else launch_save_fused(stream_, lay_, (const uint64_t*)mosaic_table_.p, wx, wy, opt_.bg_color, (uint8_t*)blend_out_bgr_.p);
         prof_end();
         HIP_OK(hipGetLastError());
     }
-    if (web) {          // sampled from the mosaic and the coverage of the same table where both lie; streams, masks and flags cross to the host
+    // the coverage from the same table, in cover_bytes_: the level-0 weights' "!= 0" bits (coverage.hip), spread to bytes
+    auto coverage = [&]() -> bool {
         if (!cover_plane_.reserve(mask_bytes / 8) || !cover_bytes_.reserve(mask_bytes)) return false;
         launch_coverage_tiles(stream_, (const uint64_t*)mosaic_table_.p, wx, wy, lay_.w_off[0], (uint8_t*)cover_plane_.p, nullptr, nullptr);
         launch_coverage_expand(stream_, (const uint8_t*)cover_plane_.p, t.rows, t.cols, (uint8_t*)cover_bytes_.p);
         HIP_OK(hipGetLastError());
-        double px2ll[6];
-        webtiles::georef_compose(t.transform, t.plane7, t.web->gps_origin, px2ll);
-        if (t.web->report) { std::memcpy(t.web->report, px2ll, sizeof px2ll); t.web->report[6] = t.rows; t.web->report[7] = t.cols; }
-        return webtiles_export(blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, cover_bytes_.p, (size_t)t.cols, px2ll, t.web->zmin, t.web->zmax, t.web->quality, opt_.bg_color,
-                               t.web->want_pixels, t.web->sink, t.web->user, jpeg_enc_, stream_);
-    }
+        return true;
+    };
+    if (web) return coverage() && export_webtiles(t, *t.web);          // sampled from the mosaic and the coverage where both lie; streams, masks and flags cross to the host
     if (!file) {
         std::vector<OutPiece> pieces;
         if (bgr) pieces.push_back({ bgr, blend_out_bgr_.p, out_bytes });
-        if (mask) {          // the coverage from the same table: the weights' "!= 0" bits (coverage.hip), spread to bytes for the caller
-            if (!cover_plane_.reserve(mask_bytes / 8) || !cover_bytes_.reserve(mask_bytes)) return false;
-            launch_coverage_tiles(stream_, (const uint64_t*)mosaic_table_.p, wx, wy, lay_.w_off[0], (uint8_t*)cover_plane_.p, nullptr, nullptr);
-            launch_coverage_expand(stream_, (const uint8_t*)cover_plane_.p, t.rows, t.cols, (uint8_t*)cover_bytes_.p);
-            HIP_OK(hipGetLastError());
+        if (mask) {
+            if (!coverage()) return false;
             pieces.push_back({ mask, cover_bytes_.p, mask_bytes });
         }
         return download(pieces);
@@ -2066,13 +2051,30 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
     return stream && write_bytes_file(t.name, stream, off[1]);
 }
 
+// the mosaic of extent t in blend_out_bgr_ and its coverage in cover_bytes_ as the map tiles of `job`: where the mosaic lies on the
+// globe (reported to the caller who asked), then sampled, reduced and encoded on the GPU (webtiles.hip)
+bool FusionMap::export_webtiles(const SaveTarget& t, const WebTilesJob& job)
+{
+    double px2ll[6];
+    webtiles::georef_compose(t.transform, t.plane7, job.gps_origin, px2ll);
+    if (job.report) { std::memcpy(job.report, px2ll, sizeof px2ll); job.report[6] = t.rows; job.report[7] = t.cols; }
+    return webtiles_export(blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, cover_bytes_.p, (size_t)t.cols, px2ll, job.zmin, job.zmax, job.quality, opt_.bg_color,
+                           job.want_pixels, job.sink, job.user, jpeg_enc_, stream_);
+}
+
+// the two-call protocols' end: save_mosaic(), then the extent handed back
+bool FusionMap::save_to_caller(SaveTarget& t, int* rows, int* cols, int* tx0, int* ty0)
+{
+    if (!save_mosaic(t)) return false;
+    *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
+    return true;
+}
+
 bool FusionMap::save_to_memory_mask(uint8_t* bgr, uint8_t* mask, int* rows, int* cols, int* tx0, int* ty0)
 {
     SaveTarget t;
     t.kind = bgr || mask ? SaveTarget::Buffer : SaveTarget::Extent; t.bgr = bgr; t.mask = mask;
-    if (!save_mosaic(t)) return false;
-    *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
-    return true;
+    return save_to_caller(t, rows, cols, tx0, ty0);
 }
 
 // the two-call protocol of pf_save_to_memory at pyramid level `level`: the extent is wy E x wx E, E = 256 >> level
@@ -2081,9 +2083,7 @@ bool FusionMap::save_to_memory_level(int level, uint8_t* bgr, int* rows, int* co
     if (!level_ok("pf_save_to_memory_level", level)) return false;
     SaveTarget t;
     t.kind = bgr ? SaveTarget::Buffer : SaveTarget::Extent; t.bgr = bgr; t.level = level;
-    if (!save_mosaic(t)) return false;
-    *rows = t.rows; *cols = t.cols; *tx0 = t.tx0; *ty0 = t.ty0;
-    return true;
+    return save_to_caller(t, rows, cols, tx0, ty0);
 }
 
 bool FusionMap::webtiles_georef(const double gps_origin[3], double px2ll[6], int* rows, int* cols)
@@ -2114,16 +2114,12 @@ bool FusionMap::webtiles(const WebTilesJob& job)
     std::vector<uint8_t> img, cover;
     t.kind = SaveTarget::Image; t.image = &img; t.mask_image = &cover;
     if (!save_mosaic(t)) { set_error("pf_webtiles: the map has no content"); return false; }
-    double px2ll[6];
-    webtiles::georef_compose(t.transform, t.plane7, job.gps_origin, px2ll);
-    if (job.report) { std::memcpy(job.report, px2ll, sizeof px2ll); job.report[6] = t.rows; job.report[7] = t.cols; }
     std::lock_guard<std::mutex> l(mu_);
     if (!set_device()) return false;
     if (!blend_out_bgr_.reserve(img.size()) || !cover_bytes_.reserve(cover.size())) return false;
     HIP_OK(hipMemcpy(blend_out_bgr_.p, img.data(), img.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(cover_bytes_.p, cover.data(), cover.size(), hipMemcpyHostToDevice));
-    return webtiles_export(blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, cover_bytes_.p, (size_t)t.cols, px2ll, job.zmin, job.zmax, job.quality, opt_.bg_color,
-                           job.want_pixels, job.sink, job.user, jpeg_enc_, stream_);
+    return export_webtiles(t, job);
 }
 
 bool FusionMap::save_file(const char* filename, SaveRoute route, int quality, bool force_bigtiff, const std::vector<ForeignTile>* foreign, bool masked)

@@ -403,6 +403,8 @@ private:
     bool        out_ring_ok_ = false;
     bool out_ring_init();
     bool download(const std::vector<OutPiece>& pieces);
+    bool export_webtiles(const SaveTarget& t, const WebTilesJob& job);                        // blend_out_bgr_ + cover_bytes_ of extent t -> the job's map tiles
+    bool save_to_caller(SaveTarget& t, int* rows, int* cols, int* tx0, int* ty0);             // save_mosaic() + the extent handed back
 #if PF_EXPERIMENTS
     bool blend_batch_per_level(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host);
 #endif
