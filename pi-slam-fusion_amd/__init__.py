@@ -198,6 +198,8 @@ def lib():
     if hasattr(L, "pf_debug_render_log") or not os.environ.get("PF_LIB"):
         L.pf_debug_render_log.argtypes = [vp, C.POINTER(C.c_longlong), C.c_int]
     L.pf_debug_culled_cells.argtypes = [vp]; L.pf_debug_culled_cells.restype = C.c_longlong
+    if hasattr(L, "pf_debug_next_homography"):          # the experiments library alone has it (csrc/c_api.cpp)
+        L.pf_debug_next_homography.argtypes = [vp, dp]; L.pf_debug_next_homography.restype = None
     L.pf_debug_level0_exact_px.argtypes = [vp]; L.pf_debug_level0_exact_px.restype = C.c_double
     L.pf_render_stats.argtypes = [vp, dp]
     L.pf_timer_read.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), dp, dp, dp]
@@ -833,6 +835,14 @@ class Map2D:
     def set_cull(self, on):
         """the cull of render_frame on / off (off: every tile of every canvas rendered, as the reference does; same mosaic)"""
         lib().pf_set_cull(self._h, 1 if on else 0)
+
+    def next_homography(self, M0):
+        """test hook of the experiments library (PF_LIB): the next accepted keyframe is warped with the 3 x 3 frame -> canvas matrix M0
+        instead of the one its pose gives; one matrix per keyframe, in the order of the calls (pf_debug_next_homography)"""
+        if not hasattr(lib(), "pf_debug_next_homography"):
+            raise RuntimeError("pf_debug_next_homography: only the experiments library has it (PF_LIB=.../libpifusion_exp.so)")
+        a = np.ascontiguousarray(M0, dtype=np.float64).reshape(9)
+        lib().pf_debug_next_homography(self._h, a.ctypes.data_as(C.POINTER(C.c_double)))
 
     def render_log(self):
         """test hook: indices of the feed() calls whose keyframes were rendered, in render order (pf_debug_render_log)"""

@@ -93,6 +93,12 @@ double pf_debug_level0_exact_px(pf_map* m) { return m ? m->impl.level0_exact_px(
 long long pf_debug_culled_tiles(pf_map* m) { return m ? m->impl.culled_tiles() : 0; }
 int pf_debug_select_counts(unsigned long long* out, int reset) { return out ? pf::read_select_counts(out, reset) : 0; }
 long pf_debug_read_last_frame(pf_map* m, void* out, size_t cap) { return m ? m->impl.read_back_last_frame(out, cap) : -1; }
+#if PF_EXPERIMENTS
+// Experiments library only, and for that reason declared here and not in include/pifusion.h: the next accepted keyframe of m is warped with
+// the frame -> canvas matrix M0 instead of the one its pose gives (one matrix per keyframe, in the order of the calls); the tile range still
+// comes from the pose.  tests/test_gpu_warp_ties.py puts the warp's coordinates on cvRound's ties with it.
+void pf_debug_next_homography(pf_map* m, const double M0[9]) { if (m && M0) m->impl.debug_next_homography(M0); }
+#endif
 unsigned pf_queue_size(pf_map* m) { return m ? m->impl.queue_size() : 0; }
 int pf_sync(pf_map* m) { return m && m->impl.sync(); }
 int pf_save(pf_map* m, const char* filename) { return m && filename && m->impl.save(filename); }

@@ -897,6 +897,9 @@ int FusionMap::frame_canvas(const QueuedFrame& f, FrameWork& w)
         dst4[2 * i + 1] = (float)((pts[2 * i + 1] - ymin) * length_pixel_inv_);
     }
     perspective_transform(src4, dst4, w.M0);
+#if PF_EXPERIMENTS
+    if (!next_M0_.empty()) { std::memcpy(w.M0, next_M0_.front().m, sizeof(w.M0)); next_M0_.pop_front(); }       // debug_next_homography()
+#endif
     w.tx = w.xmaxInt - w.xminInt; w.ty = w.ymaxInt - w.yminInt; w.L = band_num_;
     w.crows = w.ty * kElePixels; w.ccols = w.tx * kElePixels;
     return 1;

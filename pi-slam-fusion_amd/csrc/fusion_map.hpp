@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <condition_variable>
 #include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <mutex>
@@ -190,6 +191,11 @@ public:
     // and a queue that drops, the only way to tell an oracle which keyframes the map really holds; the newest 65536
     int  render_log(long long* out, int cap);
     double level0_exact_px() const { return px_level0_exact_; }
+#if PF_EXPERIMENTS
+    // test hook (pf_debug_next_homography): one frame -> canvas matrix per following accepted keyframe, used by frame_canvas() in place of
+    // perspective_transform's result and of nothing else -- tests/test_gpu_warp_ties.py chooses the warp's coordinates with it
+    void debug_next_homography(const double M0[9]) { std::lock_guard<std::mutex> l(mu_); next_M0_.emplace_back(); std::memcpy(next_M0_.back().m, M0, sizeof(double) * 9); }
+#endif
     bool high_quality() const { return opt_.high_quality_show != 0 && !single_band_; }
 
     int  num_levels() const { return band_num_ + 1; }
@@ -432,6 +438,8 @@ private:
     long long feed_seq_ = 0; std::vector<long long> render_log_;
     double px_level0_exact_ = 0;                    // experiments library, PF_CULL_EXACT_STAT (statistics of the cull, cull_exact_stat())
 #if PF_EXPERIMENTS
+    struct Mat9 { double m[9]; };
+    std::deque<Mat9> next_M0_;                      // debug_next_homography(): consumed by frame_canvas(), oldest first
     double up_rect_[kMaxLevels] = {}, up_exact_[kMaxLevels] = {}; long up_n_ = 0;
     void cull_exact_stat(const FrameWork& w);
 #endif

@@ -244,9 +244,10 @@ def to_8u(raw):
     return np.clip(np.rint((raw * F(255)).astype(np.float64)), 0, 255).astype(np.uint8)
 
 
-def canvas_geometry(shape, grid, footprint, M):
+def canvas_geometry(shape, grid, footprint, M, check_M=True):
     """renderFrame's tile range and canvas points (MultiBandMap2DCPU.cpp:380-391, :437-438; Map2DCPU.cpp:219-233, :290-296 are the same
     lines) from the grid after the feed, the footprint in plane coordinates and M, which must map the frame onto those points.
+    check_M=False: M is a matrix a test chose (tests/warp_ties.py) and is taken as it is.
     Returns ((off_x, off_y), (x0, y0, x1, y1) as dense tile indices, canvas points as float32, M as 3 x 3 float64)."""
     (w, h, offx, offy), (mnx, mny, _, _, ele_size, length_pixel) = grid
     pts = np.asarray(footprint, np.float64).reshape(4, 2)
@@ -263,7 +264,7 @@ def canvas_geometry(shape, grid, footprint, M):
     rows, cols = shape[:2]
     corners = np.array([[0, 0], [cols, 0], [0, rows], [cols, rows]], np.float64)
     proj = (M @ np.c_[corners, np.ones(4)].T).T
-    assert np.abs(proj[:, :2] / proj[:, 2:] - canvas).max() < 1e-3, "M does not map the frame onto its canvas points"
+    assert not check_M or np.abs(proj[:, :2] / proj[:, 2:] - canvas).max() < 1e-3, "M does not map the frame onto its canvas points"
     return (offx, offy), (x0, y0, x1, y1), canvas, M
 
 
@@ -290,13 +291,13 @@ class ModelMap:
     def num_levels(self):
         return self.L + 1
 
-    def feed(self, bgr, grid, footprint, M):
+    def feed(self, bgr, grid, footprint, M, check_M=True):
         """One keyframe.  grid: (dims, geo) of the map after this feed (dims = [w, h, off_x, off_y], geo = [min_x, min_y, max_x,
         max_y, ele_size, length_pixel]); footprint: the 4 plane points of the frame corners (4 x 2); M: the 3x3 homography from
-        the frame to the canvas."""
+        the frame to the canvas (check_M=False: one that a test injected, which need not map the frame onto the canvas points)."""
         self.grid_ = grid
         self._out = {}
-        (offx, offy), (x0, y0, x1, y1), canvas, M = canvas_geometry(bgr.shape, grid, footprint, M)
+        (offx, offy), (x0, y0, x1, y1), canvas, M = canvas_geometry(bgr.shape, grid, footprint, M, check_M)
         rows, cols = bgr.shape[:2]
         tx, ty = x1 - x0, y1 - y0
         self.last = ([x0 + offx, y0 + offy, tx, ty], canvas, M)
@@ -497,11 +498,11 @@ class ModelMapSingleBand:
         self.frozen = True
         return self
 
-    def feed(self, bgr, grid, footprint, M):
+    def feed(self, bgr, grid, footprint, M, check_M=True):
         """The arguments of ModelMap.feed; a fourth channel of the frame is ignored (the map takes the first three)."""
         assert not getattr(self, "frozen", False), "this model is shared between tests: build another one"
         self.grid_ = grid
-        (offx, offy), (x0, y0, x1, y1), canvas, M = canvas_geometry(bgr.shape, grid, footprint, M)
+        (offx, offy), (x0, y0, x1, y1), canvas, M = canvas_geometry(bgr.shape, grid, footprint, M, check_M)
         rows, cols = bgr.shape[:2]
         tx, ty = x1 - x0, y1 - y0
         self.last = ([x0 + offx, y0 + offy, tx, ty], canvas, M)
