@@ -92,7 +92,17 @@ int     pf_prepare(pf_map* m, const double plane[7], const double cam[6],
 /* Map2D::feed(img, pose), MultiBandMap2DCPU.cpp:288-309.  Host BGR8 (or BGRA8) frame; the
  * rows are copied to HBM as they lie (img->step is kept) by one blocking linear H2D copy, so
  * the caller may release its pixels when feed returns (the reference keeps a refcounted
- * cv::Mat instead).                                                          */
+ * cv::Mat instead).
+ * When HBM runs out (a tile slab, the frame workspace or a frame slot cannot be allocated) the feed that meets it
+ * returns 0 with the reason in pf_last_error() and costs that keyframe alone: nothing of it is in the map or in the
+ * cull's bounds, the tiles it created before the failure stay as tiles without pyramid, keyframes fed before and
+ * after it are fused exactly as if it had never been fed, and the same keyframe may be fed again once memory is back.
+ * With a lookahead the tiles and the workspace of a keyframe are allocated when it is admitted, inside its own feed
+ * call, so this holds there as well.  What can still fail when a waiting keyframe is rendered later (a launch, the
+ * one-off weight plane) is met by the call that renders it: a pf_feed returns 0 although its own keyframe is in (to
+ * feed it again is harmless: the select is idempotent), a reader returns its data.  Every keyframe lost either way is
+ * counted (pf_stats_failed) and reported by the next pf_sync; a frame that never got its slot in HBM was not
+ * accepted and is not.                                                                                           */
 int     pf_feed(pf_map* m, const pf_image* img, const double pose[7]);
 /* Same, frame already resident in HBM (img->data is a device pointer that
  * must stay valid -- and unchanged -- until pf_sync: the frame is read when its keyframe is rendered, which with
@@ -113,7 +123,19 @@ int     pf_debug_select_counts(unsigned long long* out, int reset);
  * taken out of it and holds for the cull's lookahead are not counted: they no longer occupy a place in the queue and cannot be dropped. */
 unsigned pf_queue_size(pf_map* m);
 /* drain the feed queue, render the keyframes that wait for the cull's lookahead (pf_options.lookahead) and wait for the
- * device stream (no reference counterpart: the reference is synchronous on the CPU).  Returns 0 if a render failed.       */
+ * device stream (no reference counterpart: the reference is synchronous on the CPU).
+ * Returns 0 ONCE, with the message of the newest failure in pf_last_error() of the calling thread, when an accepted keyframe was
+ * lost to a failure (an allocation, a launch) since the previous pf_sync -- inside a pf_feed (which returned 0 then), while a
+ * reader rendered what waited, or on the render thread of a thread=1 map, whose pf_feed cannot know.  The queue is drained and
+ * the device waited for all the same, so the next pf_sync returns 1 unless more was lost; pf_stats_failed counts the keyframes
+ * and pf_debug_render_log names the ones that are in.
+ * The rule behind it: a keyframe enters the bounds that later keyframes are culled against only when nothing that needs memory
+ * is left of its render -- its tiles exist and the workspace holds its canvas -- so an allocation failure never leaves cells that
+ * were skipped for a keyframe that is not there.  A failure of the render itself after that (a launch error) loses the keyframe
+ * as well, and cells of its canvas may then lack pixels of keyframes admitted after it: that is never silent -- this call
+ * returns 0 and the count moves -- and the caller should rebuild the map.
+ * The readers (tile access, blend, save, statistics, pf_debug_*) render what waits, ignore such a failure and return their data
+ * of the map as it is; the failure stays pending for pf_sync.                                                                  */
 int     pf_sync(pf_map* m);
 /* Map2D::save(filename), MultiBandMap2DCPU.cpp:779-847.  Writes PNG (.png),
  * JPEG (.jpg / .jpeg, either case: quality 95, 4:2:0, cv::imwrite's default;
@@ -524,6 +546,9 @@ void    pf_debug_form_counts(long long out[8]);
 long long pf_debug_compact_launches(void);
 /* frames rendered / rejected since creation */
 int     pf_stats(pf_map* m, long long* rendered, long long* rejected, long long* dropped);
+/* ... and `failed`: keyframes that were accepted (not rejected, not dropped from the queue) and are not in the map because an allocation
+ * or a launch failed (see pf_feed, pf_sync).  Any of the four may be NULL. */
+int     pf_stats_failed(pf_map* m, long long* rendered, long long* rejected, long long* dropped, long long* failed);
 /* Allocator hint, no reference counterpart (MultiBandMap2DCPUEle's cv::Mat tiles, MultiBandMap2DCPU.h:32-51,
  * come from the heap one by one): HBM for n_tiles more tiles is allocated and touched now instead of slab by
  * slab while keyframes are being fused.  Call it after pf_prepare (which empties the store).                  */

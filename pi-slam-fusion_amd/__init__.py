@@ -200,6 +200,11 @@ def lib():
     L.pf_debug_culled_cells.argtypes = [vp]; L.pf_debug_culled_cells.restype = C.c_longlong
     if hasattr(L, "pf_debug_next_homography"):          # the experiments library alone has it (csrc/c_api.cpp)
         L.pf_debug_next_homography.argtypes = [vp, dp]; L.pf_debug_next_homography.restype = None
+    if hasattr(L, "pf_debug_tile_store"):               # likewise
+        L.pf_debug_tile_store.argtypes = [vp, C.c_int, C.c_int, C.c_int]; L.pf_debug_tile_store.restype = None
+        L.pf_debug_fail_workspace.argtypes = [vp, C.c_int]; L.pf_debug_fail_workspace.restype = None
+    if hasattr(L, "pf_stats_failed") or not os.environ.get("PF_LIB"):
+        L.pf_stats_failed.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.pf_debug_level0_exact_px.argtypes = [vp]; L.pf_debug_level0_exact_px.restype = C.c_double
     L.pf_render_stats.argtypes = [vp, dp]
     L.pf_timer_read.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), dp, dp, dp]
@@ -843,6 +848,25 @@ class Map2D:
             raise RuntimeError("pf_debug_next_homography: only the experiments library has it (PF_LIB=.../libpifusion_exp.so)")
         a = np.ascontiguousarray(M0, dtype=np.float64).reshape(9)
         lib().pf_debug_next_homography(self._h, a.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def debug_tile_store(self, slab_slots, fail_from=0, fail_count=0):
+        """test hook of the experiments library (PF_LIB): tile slabs of slab_slots tiles from now on (0: the default size), and of the slabs
+        asked for from this call on those numbered fail_from .. fail_from + fail_count - 1 are refused by hipMalloc (pf_debug_tile_store)"""
+        if not hasattr(lib(), "pf_debug_tile_store"):
+            raise RuntimeError("pf_debug_tile_store: only the experiments library has it (PF_LIB=.../libpifusion_exp.so)")
+        lib().pf_debug_tile_store(self._h, int(slab_slots), int(fail_from), int(fail_count))
+
+    def debug_fail_workspace(self, n):
+        """test hook of the experiments library: the next n calls that size the frame workspace meet a hipMalloc that refuses"""
+        if not hasattr(lib(), "pf_debug_fail_workspace"):
+            raise RuntimeError("pf_debug_fail_workspace: only the experiments library has it (PF_LIB=.../libpifusion_exp.so)")
+        lib().pf_debug_fail_workspace(self._h, int(n))
+
+    def failed(self):
+        """keyframes accepted and then lost to an allocation or launch failure (pf_stats_failed)"""
+        n = C.c_longlong()
+        lib().pf_stats_failed(self._h, None, None, None, C.byref(n))
+        return n.value
 
     def render_log(self):
         """test hook: indices of the feed() calls whose keyframes were rendered, in render order (pf_debug_render_log)"""

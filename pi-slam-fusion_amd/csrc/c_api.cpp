@@ -98,6 +98,12 @@ long pf_debug_read_last_frame(pf_map* m, void* out, size_t cap) { return m ? m->
 // the frame -> canvas matrix M0 instead of the one its pose gives (one matrix per keyframe, in the order of the calls); the tile range still
 // comes from the pose.  tests/test_gpu_warp_ties.py puts the warp's coordinates on cvRound's ties with it.
 void pf_debug_next_homography(pf_map* m, const double M0[9]) { if (m && M0) m->impl.debug_next_homography(M0); }
+// Allocation failures on request (tests/test_gpu_alloc_failure.py), injected as real refusals of hipMalloc: the request is for 2^60 bytes.
+// pf_debug_tile_store: from now on the tile store opens slabs of slab_slots tiles (0: its default of about 256 MiB; > 0 also closes the slab
+// in progress, so the next new tile opens the first slab counted), and of the slabs it asks for from this call on, those numbered fail_from
+// .. fail_from + fail_count - 1 (0-based) fail.  pf_debug_fail_workspace: the next n calls that size the frame workspace fail.
+void pf_debug_tile_store(pf_map* m, int slab_slots, int fail_from, int fail_count) { if (m) m->impl.debug_tile_store(slab_slots, fail_from, fail_count); }
+void pf_debug_fail_workspace(pf_map* m, int n) { if (m) m->impl.debug_fail_workspace(n); }
 #endif
 unsigned pf_queue_size(pf_map* m) { return m ? m->impl.queue_size() : 0; }
 int pf_sync(pf_map* m) { return m && m->impl.sync(); }
@@ -582,6 +588,8 @@ int pf_profile_reset(pf_map* m) { if (!m) return 0; m->impl.profile_reset(); ret
 int pf_reserve_tiles(pf_map* m, long long n_tiles) { return m && m->impl.reserve_tiles(n_tiles) ? 1 : 0; }
 int pf_render_stats(pf_map* m, double out4[4]) { if (!m || !out4) return 0; m->impl.render_stats(out4); return 1; }
 int pf_stats(pf_map* m, long long* rendered, long long* rejected, long long* dropped) { if (!m) return 0; m->impl.stats(rendered, rejected, dropped); return 1; }
+int pf_stats_failed(pf_map* m, long long* rendered, long long* rejected, long long* dropped, long long* failed)
+{ if (!m) return 0; m->impl.stats(rendered, rejected, dropped, failed); return 1; }
 int pf_timer_read(pf_map* m, int cap, const char** names, long long* calls, double* mean_s, double* min_s, double* max_s)
 {
     return m ? m->impl.timer_read(cap, names, calls, mean_s, min_s, max_s) : 0;

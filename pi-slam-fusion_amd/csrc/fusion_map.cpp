@@ -117,19 +117,31 @@ Tile* TileStore::find(int ix, int iy)
 bool TileStore::add_chunk(size_t slots)
 {
     void* p = nullptr;
-    if (hipMalloc(&p, slots * slot_bytes_) != hipSuccess) { set_error("tile store: hipMalloc failed"); return false; }
+    size_t bytes = slots * slot_bytes_;
+#if PF_EXPERIMENTS
+    if (dbg_count_ > 0) { const long no = dbg_no_++; if (no >= dbg_from_ && no < dbg_from_ + dbg_count_) bytes = (size_t)1 << 60; }      // debug_limits()
+#endif
+    // (a refused hipMalloc stays behind as the thread's last HIP error: taken off here, or the next launch check reports it as its own)
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("tile store: hipMalloc failed"); return false; }
     chunks_.push_back({ (char*)p, slots });
     return true;
+}
+
+size_t TileStore::slab_slots() const
+{
+#if PF_EXPERIMENTS
+    if (dbg_slab_) return dbg_slab_;
+#endif
+    return std::max<size_t>(16, (256u << 20) / slot_bytes_);
 }
 
 Tile* TileStore::get_or_create(int ix, int iy)
 {
     auto it = map_.find(key(ix, iy));
     if (it != map_.end()) return &it->second;
-    if (chunks_.empty()) { if (!add_chunk(std::max<size_t>(16, (256u << 20) / slot_bytes_))) return nullptr; cur_ = 0; next_in_chunk_ = 0; }
+    if (chunks_.empty()) { if (!add_chunk(slab_slots())) return nullptr; cur_ = 0; next_in_chunk_ = 0; }
     if (next_in_chunk_ == chunks_[cur_].slots) {
-        // slabs of ~256 MiB: few hipMallocs, tiles of one neighbourhood stay close in HBM
-        if (cur_ + 1 == chunks_.size() && !add_chunk(std::max<size_t>(16, (256u << 20) / slot_bytes_))) return nullptr;
+        if (cur_ + 1 == chunks_.size() && !add_chunk(slab_slots())) return nullptr;
         cur_++; next_in_chunk_ = 0;
     }
     Tile t;
@@ -160,7 +172,7 @@ bool DevBuf::reserve(size_t bytes)
     if (bytes <= cap) return true;
     release();
     const size_t want = bytes + bytes / 4;
-    if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; set_error("hipMalloc failed"); return false; }
+    if (hipMalloc(&p, want) != hipSuccess) { (void)hipGetLastError(); p = nullptr; set_error("hipMalloc failed"); return false; }
     cap = want;
     return true;
 }
@@ -336,11 +348,12 @@ void FusionMap::render_stats(double out[4])
     out[0] = (double)n_with_pixels_; out[1] = px_level0_; out[2] = px_owned_; out[3] = (double)store_.size();
 }
 
-void FusionMap::stats(long long* rendered, long long* rejected, long long* dropped)
+void FusionMap::stats(long long* rendered, long long* rejected, long long* dropped, long long* failed)
 {
     std::lock_guard<std::mutex> l(mu_); (void)drain();
     if (rendered) *rendered = n_rendered_;
     if (rejected) *rejected = n_rejected_;
+    if (failed) *failed = n_failed_;
     std::lock_guard<std::mutex> q(qmu_);
     if (dropped) *dropped = n_dropped_;
 }
@@ -444,14 +457,14 @@ int FusionMap::acquire_slot(size_t bytes)
             if (s.cap < bytes) {
                 if (s.dev) (void)hipFree(s.dev);
                 s.dev = nullptr; s.cap = 0;
-                if (hipMalloc((void**)&s.dev, bytes + 64) != hipSuccess) { set_error("frame slot hipMalloc failed"); return -1; }
+                if (hipMalloc((void**)&s.dev, bytes + 64) != hipSuccess) { (void)hipGetLastError(); set_error("frame slot hipMalloc failed"); return -1; }
                 s.cap = bytes;
             }
             return (int)i;
         }
         if (slots_.size() < limit) {
             FrameSlot s;
-            if (hipMalloc((void**)&s.dev, bytes + 64) != hipSuccess) { set_error("frame slot hipMalloc failed"); return -1; }
+            if (hipMalloc((void**)&s.dev, bytes + 64) != hipSuccess) { (void)hipGetLastError(); set_error("frame slot hipMalloc failed"); return -1; }
             s.cap = bytes;
             if (hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return -1; }
             slots_.push_back(s);
@@ -639,7 +652,9 @@ void FusionMap::worker()
         }
         {
             std::lock_guard<std::mutex> l(mu_);
-            if (valid_ && set_device()) render_frame(f);          // in; rendered once opt_.lookahead more keyframes are, or ...
+            // in; rendered once opt_.lookahead more keyframes are, or ...  (a keyframe lost on the way -- here or in the drain() below -- is
+            // counted where it is lost, keyframe_lost(), and the next sync() says so: this thread has nobody to return false to)
+            if (valid_ && set_device()) (void)render_frame(f);
             else release_slot(f);
         }
         bool idle;
@@ -664,10 +679,16 @@ bool FusionMap::sync()
         idle_cv_.wait(q, [this] { return queue_.empty() && !worker_busy_; });
     }
     std::lock_guard<std::mutex> l(mu_);
-    if (!set_device() || !drain()) return false;
+    if (!set_device()) return false;
+    const bool drained = drain();
+    // keyframes lost since the last sync() -- in a feed, in a reader's drain, on the render thread or just now: said once, with the message
+    // of the newest of them (FusionMap::stats counts them)
+    const bool lost = fail_pending_;
+    fail_pending_ = false;
     HIP_OK(sync_all());
     prof_harvest();
-    return true;
+    if (lost) { set_error(fail_msg_); return false; }
+    return drained;
 }
 
 // the tiles (dense index) a box of plane coordinates touches
@@ -759,7 +780,17 @@ bool FusionMap::render_frame(const QueuedFrame& f)
         if (lookahead_ok()) {
             // the keyframe's own lower bounds enter the tiles' wlb NOW: the keyframes ahead of it in the queue are decided against them
             if (!tiles_pool_.empty()) { p.tiles = std::move(tiles_pool_.back()); tiles_pool_.pop_back(); }
-            pre_raise(w, p.tiles);
+            // From here on later keyframes are culled against this one, so whatever of its render can fail for want of memory is done first:
+            // the workspace of its canvas, then its tiles.  A failure loses this keyframe inside its own feed call, as without a lookahead,
+            // and nothing of it is in any wlb
+            if (!reserve_frame_workspace(w) || !pre_raise(w, p.tiles)) {
+                if (p.lat.sx.capacity() && lat_pool_.size() < 8) lat_pool_.push_back(std::move(p.lat));
+                if (p.tiles.capacity() && tiles_pool_.size() < 8) tiles_pool_.push_back(std::move(p.tiles));
+                pending_.pop_back();
+                release_slot(f);
+                keyframe_lost();
+                return false;
+            }
             p.pre_raised = true;
             since_drain_++;
             keep = std::min<size_t>((size_t)opt_.lookahead, 2 * (size_t)since_drain_ / 3);
@@ -773,8 +804,9 @@ bool FusionMap::render_frame(const QueuedFrame& f)
 }
 
 // The weight bounds of an admitted keyframe go into its tiles' wlb (Lattice::raise_bounds; build_tile_table does not work them out again).
-// Creates the canvas' tiles, as Apply's tile loop does (.cpp:478-492), and remembers them for the render.
-void FusionMap::pre_raise(FrameWork& w, std::vector<Tile*>& tiles)
+// Creates the canvas' tiles, as Apply's tile loop does (.cpp:478-492), and remembers them for the render.  All tiles first, then the bounds:
+// when the store cannot grow (false; the tiles made so far stay, fresh) no wlb holds a bound of a keyframe that will not be rendered.
+bool FusionMap::pre_raise(FrameWork& w, std::vector<Tile*>& tiles)
 {
     tiles.assign((size_t)w.tx * w.ty, nullptr);
     const bool sharded = opt_.shard_count > 1;
@@ -783,10 +815,13 @@ void FusionMap::pre_raise(FrameWork& w, std::vector<Tile*>& tiles)
             const int sx = w.xminInt + x + off_x_, sy = w.yminInt + y + off_y_;
             if (sharded && tile_owner(opt_.shard_count, opt_.shard_block, sx, sy) != opt_.shard_rank) continue;
             Tile* t = store_.get_or_create(sx, sy);
-            if (!t) { tiles.clear(); return; }                // HBM exhausted: build_tile_table meets it again and reports it
+            if (!t) { tiles.clear(); return false; }          // HBM exhausted
             tiles[(size_t)y * w.tx + x] = t;                  // (references into the store stay valid while it grows)
-            w.lat->raise_bounds(x, y, opt_.weight_type, t->wlb);
         }
+    for (int y = 0; y < w.ty; y++)
+        for (int x = 0; x < w.tx; x++)
+            if (Tile* t = tiles[(size_t)y * w.tx + x]) w.lat->raise_bounds(x, y, opt_.weight_type, t->wlb);
+    return true;
 }
 
 void FusionMap::release_slot(const QueuedFrame& f)
@@ -801,13 +836,24 @@ bool FusionMap::drain()
     since_drain_ = 0;
     if (pending_.empty()) return true;
     if (!set_device()) return false;
-    while (!pending_.empty())
-        if (!render_front()) return false;
-    return true;
+    // (a keyframe that fails costs that keyframe: the others that wait are rendered all the same, or a reader -- which has no use for
+    // the result -- would look at a map short of them too)
+    bool ok = true;
+    while (!pending_.empty()) ok = render_front() && ok;
+    return ok;
 }
 
-// stages 4 onwards of renderFrame for the oldest keyframe that waits
+// stages 4 onwards of renderFrame for the oldest keyframe that waits.  When they fail the keyframe is lost, and counted: keyframes admitted
+// after it may have been culled against its bounds (reserve_frame_workspace and the tiles are seen to at admission for that reason; what is
+// left is the launches themselves and the one-off weight plane), so the caller of this call or of the next sync() has to hear of it
 bool FusionMap::render_front()
+{
+    const bool ok = render_front_stages();
+    if (!ok) keyframe_lost();
+    return ok;
+}
+
+bool FusionMap::render_front_stages()
 {
     struct Pop {            // the keyframe leaves the queue whatever happens to it (its lattice's buffers go back to the pool)
         FusionMap* m;
@@ -830,6 +876,7 @@ bool FusionMap::render_front()
     w.cull = p.cull;
     w.pre_raised = p.pre_raised;
     w.tiles_known = p.tiles.size() == (size_t)p.tx * p.ty ? p.tiles.data() : nullptr;
+    if (w.pre_raised && !w.tiles_known) { set_error("render_front: a keyframe admitted without its tiles"); return false; }      // (render_frame admits none)
     w.src = f.ext ? f.ext : slots_[f.slot].dev;
     w.lat = &p.lat;
     Section sec_apply(this, T_APPLY);          // the reference times its tile loop under this name (.cpp:476-555); here: table, need rectangles, launch
@@ -1010,6 +1057,17 @@ bool FusionMap::reserve_frame_workspace(FrameWork& w)
         else if (g_[i].cap < n * 3 * es || wgt_[i].cap < n * 4) grow = true;
     }
     if (table_cap_ < (size_t)tx * ty) grow = true;
+#if PF_EXPERIMENTS
+    if (dbg_fail_workspace_ > 0) {
+        // debug_fail_workspace(): this call meets a hipMalloc that refuses -- 2^60 bytes asked of the first buffer of the workspace, which
+        // goes the way DevBuf::reserve sends a buffer that cannot grow (released; the next call that needs it allocates it again)
+        dbg_fail_workspace_--;
+        HIP_OK(sync_all());
+        DevBuf& b = single_band_ ? table_dev_[0] : (fused ? gw_[1] : g_[0]);
+        if (&b == &table_dev_[0]) table_cap_ = 0;
+        return b.reserve((size_t)1 << 60);
+    }
+#endif
     if (!grow) return true;
     HIP_OK(sync_all());
     for (int i = 0; i <= L; i++) {

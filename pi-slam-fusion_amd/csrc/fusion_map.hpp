@@ -53,6 +53,16 @@ public:
     void  clear();
     size_t size() const { return map_.size(); }
     template <class F> void for_each(F f) { for (auto& kv : map_) f((int)(int32_t)(kv.first >> 32), (int)(int32_t)(kv.first & 0xffffffffu), kv.second); }
+#if PF_EXPERIMENTS
+    // test hook (pf_debug_tile_store): from now on get_or_create opens slabs of slab_slots tiles (0: the default size; > 0 also closes the
+    // slab in progress, so that the next new tile opens slab 0), and of the slabs asked for from now on those numbered fail_from ..
+    // fail_from + fail_count - 1 are asked of hipMalloc at 2^60 bytes, which it refuses as it refuses a request the device cannot meet
+    void debug_limits(int slab_slots, int fail_from, int fail_count)
+    {
+        dbg_slab_ = slab_slots > 0 ? (size_t)slab_slots : 0; dbg_no_ = 0; dbg_from_ = fail_from; dbg_count_ = fail_count;
+        if (dbg_slab_ && !chunks_.empty()) next_in_chunk_ = chunks_[cur_].slots;
+    }
+#endif
 private:
     static uint64_t key(int ix, int iy) { return ((uint64_t)(uint32_t)ix << 32) | (uint32_t)iy; }
     std::unordered_map<uint64_t, Tile> map_;
@@ -60,6 +70,10 @@ private:
     std::vector<Chunk> chunks_;                   // chunks_[cur_] is being filled, later ones are reserved ahead
     size_t slot_bytes_ = 0, cur_ = 0, next_in_chunk_ = 0;
     bool   add_chunk(size_t slots);
+    size_t slab_slots() const;                    // slabs of ~256 MiB: few hipMallocs, tiles of one neighbourhood stay close in HBM
+#if PF_EXPERIMENTS
+    size_t dbg_slab_ = 0; long dbg_no_ = 0, dbg_from_ = 0, dbg_count_ = 0;
+#endif
 };
 
 struct DevBuf {
@@ -195,6 +209,10 @@ public:
     // test hook (pf_debug_next_homography): one frame -> canvas matrix per following accepted keyframe, used by frame_canvas() in place of
     // perspective_transform's result and of nothing else -- tests/test_gpu_warp_ties.py chooses the warp's coordinates with it
     void debug_next_homography(const double M0[9]) { std::lock_guard<std::mutex> l(mu_); next_M0_.emplace_back(); std::memcpy(next_M0_.back().m, M0, sizeof(double) * 9); }
+    // test hooks (pf_debug_tile_store / pf_debug_fail_workspace): allocation failures on request -- tests/test_gpu_alloc_failure.py.  Neither
+    // renders what waits: a test arms them between two feeds without emptying the lookahead window
+    void debug_tile_store(int slab_slots, int fail_from, int fail_count) { std::lock_guard<std::mutex> l(mu_); store_.debug_limits(slab_slots, fail_from, fail_count); }
+    void debug_fail_workspace(int n) { std::lock_guard<std::mutex> l(mu_); dbg_fail_workspace_ = n; }
 #endif
     bool high_quality() const { return opt_.high_quality_show != 0 && !single_band_; }
 
@@ -223,7 +241,7 @@ public:
     void profile_enable(int mode);
     int  profile_read(int cap, const char** names, double* ms, long long* launches, double* bytes, double* bytes_run = nullptr);
     void profile_reset();
-    void stats(long long* rendered, long long* rejected, long long* dropped);
+    void stats(long long* rendered, long long* rejected, long long* dropped, long long* failed = nullptr);
     void render_stats(double out[4]);
     int  timer_read(int cap, const char** names, long long* calls, double* mean_s, double* min_s, double* max_s);
     void timer_reset();
@@ -372,10 +390,20 @@ private:
     std::vector<Lattice> lat_pool_;                 // buffers of rendered keyframes' lattices, reused
     std::vector<std::vector<Tile*>> tiles_pool_;
     bool lookahead_ok() const { return opt_.lookahead > 0 && (single_band_ || (opt_.fused == 1 && band_num_ >= 1)) && cull_on_; }     // wherever the cull runs
-    bool render_front();                            // renders pending_.front() and removes it
+    bool render_front();                            // renders pending_.front() and removes it; a failure is counted (keyframe_lost)
+    bool render_front_stages();                     // ... its stages 4 onwards
     bool drain();                                   // ... all of them; mu_ held.  First thing every reader of tiles, flags or counters does
     void release_slot(const QueuedFrame& f);
-    void pre_raise(FrameWork& w, std::vector<Tile*>& tiles);
+    bool pre_raise(FrameWork& w, std::vector<Tile*>& tiles);
+    // A keyframe that was accepted (its geometry is in, the grid has advanced) and is not in the map, because an allocation or a launch
+    // failed: counted, and the message kept for the next sync() -- whichever thread and whichever call met the failure (mu_ held)
+    void keyframe_lost() { n_failed_++; fail_pending_ = true; fail_msg_ = last_error(); }
+    long long n_failed_ = 0;
+    bool fail_pending_ = false;
+    std::string fail_msg_;
+#if PF_EXPERIMENTS
+    int dbg_fail_workspace_ = 0;                    // debug_fail_workspace(): reserve_frame_workspace calls that still have to fail
+#endif
     int  frame_canvas(const QueuedFrame& f, FrameWork& w);
     bool build_tile_table(const QueuedFrame& f, FrameWork& w);
     bool reserve_frame_workspace(FrameWork& w);

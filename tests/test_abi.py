@@ -138,6 +138,17 @@ def test_product_library_carries_the_product_kernels_only():
         assert len(set(re.findall(rb"_ZN2pf8k_levelsIL[0-9A-Za-z_]+?EEEvNS_10LevelBatchE", exp))) > 10
 
 
+def test_allocation_failure_hooks_are_in_the_experiments_library_alone():
+    """pf_debug_tile_store / pf_debug_fail_workspace (tests/test_gpu_alloc_failure.py makes hipMalloc refuse with them) are test
+    infrastructure: not in the product library, not declared in include/pifusion.h; pf_stats_failed is the product's"""
+    here = os.path.join(ROOT, "pi-slam-fusion_amd")
+    prod, exp = open(os.path.join(here, "libpifusion.so"), "rb").read(), open(os.path.join(here, "libpifusion_exp.so"), "rb").read()
+    header = open(os.path.join(ROOT, "include", "pifusion.h"), "rb").read()
+    for name in (b"pf_debug_tile_store", b"pf_debug_fail_workspace"):
+        assert name not in prod and name in exp and name not in header, name
+    assert b"pf_stats_failed" in prod and b"pf_stats_failed" in header
+
+
 def test_product_library_reads_only_its_documented_environment():
     """csrc/env.hpp: the product library reads PF_CULL, PF_ROCTX, PF_DIST_VERIFY and PF_COPY_THREADS; A/B switches and timing-only
     diagnostics (some of which produce wrong tiles) exist in the experiments build alone -- their names are not even among the
