@@ -541,6 +541,15 @@ void    pf_set_cull(pf_map* m, int on);
  * [1] block form gathering the weight plane, [2] LDS-staged source patch, [3] rolling strips, [4] 64x64 blocks, [5] 64x28 blocks,
  * [6] stamped instantiation, [7] launches whose tile table travelled in the kernel arguments.  Diagnostics (variant tests). */
 void    pf_debug_form_counts(long long out[8]);
+/* By which rule the blocks of those launches decided whether they run, since the library was loaded (k_levels; which one a launch takes
+ * follows from the size of the keyframe's canvas alone).  Per launch with a level-0 job: [0] tile table in the kernel arguments and the
+ * block tests itself against it (need_r0), [1] need rectangles, [2] no filter, every block runs, [3] tile table staged and copied in the
+ * stream instead of travelling in the arguments.  Per upper-level job: [4] need bitmap, [5] need rectangles, [6] no filter.  On the host:
+ * [7] keyframes whose plan merged rectangles (more cells than a level-0 job carries rectangles, or than an upper-level job does).
+ * Counted for launches of k_levels only: the experiments library's rolling-strip form (PF_STRIPS) moves none of them, and its compact
+ * grid (PF_COMPACT), whose level-0 blocks lie inside the rectangles by construction, counts as [1].
+ * Diagnostics (tests/test_gpu_large_canvas.py). */
+void    pf_debug_admission_counts(long long out[8]);
 /* ... and how many of them ran their level-0 job on the compact grid (one workgroup per block inside the need rectangles of a shard / of
  * the cull, instead of one per block of the canvas' bounding box) */
 long long pf_debug_compact_launches(void);

@@ -299,6 +299,7 @@ struct LevelPlan {
     uint32_t need_bits[kMaxLevels][kNeedWords];     // the upper levels' need bitmaps (need_n[i] blocks; 0: none)
     double blocks_run0;                             // level-0 blocks that run
     bool partial;                                   // the cull or a shard leaves blocks out
+    bool merged;                                    // some level had more rectangles than its job carries: pairs were merged (diagnostics)
     int L, tx, ty, BH, reach0;
     // scratch, kept between keyframes for its capacity
     std::vector<u128> cell_rows, colmask;           // rendered cells of the canvas, one 128-bit row per cell row; exact_level0_blocks' column masks
@@ -306,7 +307,7 @@ struct LevelPlan {
     struct R { int x0, y0, x1, y1; };
     std::vector<R> lv[kMaxLevels];
 
-    void reset() { blocks_run0 = 0; partial = false; for (int i = 0; i < kMaxLevels; i++) { nrect[i] = 0; need_n[i] = 0; } }
+    void reset() { blocks_run0 = 0; partial = false; merged = false; for (int i = 0; i < kMaxLevels; i++) { nrect[i] = 0; need_n[i] = 0; } }
     int grid_x(int i) const { return (C[i].x1 - C[i].x0 + 63) / 64; }
     int grid_y(int i) const { return (C[i].y1 - C[i].y0 + BH - 1) / BH; }
     int need_count(int i) const { int n = 0; for (int k = 0; k < (need_n[i] + 31) / 32; k++) n += __builtin_popcount(need_bits[i][k]); return n; }
@@ -341,6 +342,7 @@ struct LevelPlan {
     bool plan(const uint64_t* table, int tx_, int ty_, int L_, const Win& box, const CellList& cells, bool sharded, bool culled_any, int fused, int BH_, int reach0_)
     {
         L = L_; tx = tx_; ty = ty_; BH = BH_; reach0 = reach0_;
+        merged = false;
         const int crows = ty * kElePixels, ccols = tx * kElePixels;
         for (int i = L - 1; i >= 0; i--) {
             // the origin stays even (a block's quads and its part of level i+1 start on even pixels): a box of 64-pixel cells is odd at level 6
@@ -404,6 +406,7 @@ struct LevelPlan {
             std::vector<R>& v = lv[i];
             auto area = [](const R& r) { return (long)(r.x1 - r.x0) * (r.y1 - r.y0); };
             const int cap = i == 0 ? kMaxRects : kMaxRectsUpper;       // what a job of this level can carry (plan_limits.hpp)
+            if ((int)v.size() > cap) merged = true;
             while ((int)v.size() > cap) {
                 size_t ba = 0, bb = 1; long best = -1;
                 for (size_t p = 0; p < v.size(); p++)

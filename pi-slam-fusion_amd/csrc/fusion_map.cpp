@@ -1148,6 +1148,7 @@ void FusionMap::plan_fused_levels(FrameWork& w)
     // (the level-0 job carries rectangles wherever the plan consults the reach)
     const bool rects = w.plan.plan(table_tmp_.data(), w.tx, w.ty, w.L, w.pb, w.cells, w.sharded, w.culled_any, opt_.fused, BHr,
                                    level0_need_reach(lay_, w.table_args ? w.tx * w.ty : 0, 1));
+    if (rects && w.plan.merged) count_merged_plan();
     const Win& C0 = w.plan.C[0];
     px_level0_ += rects ? w.plan.blocks_run0 * 64 * BHr : (double)(C0.x1 - C0.x0) * (C0.y1 - C0.y0);
 #if PF_EXPERIMENTS

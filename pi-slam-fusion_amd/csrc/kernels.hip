@@ -2014,6 +2014,29 @@ static long long g_form_counts[8] = {};
 void read_form_counts(long long out[8]) { for (int i = 0; i < 8; i++) out[i] = g_form_counts[i]; }
 static long long g_compact_launches = 0;                          // pipelined launches whose level-0 job ran on the compact grid (LevelBatch::compact0)
 long long read_compact_launches() { return g_compact_launches; }
+// by which rule the blocks of the k_levels launches decided whether they run (the branches of its prologue, in their order), since the
+// library was loaded.  Per launch with a level-0 job: 0 the tile table in the kernel arguments and the block's own test against it (need_r0),
+// 1 need rectangles, 2 no filter, 3 the table was staged, not in the arguments; per upper-level job: 4 need bitmap, 5 need rectangles,
+// 6 no filter; 7 (host, count_merged_plan) keyframes whose plan merged rectangles.  tests/test_gpu_large_canvas.py asserts that a canvas
+// of a given size took the form its size implies.  (launch_strips returns before this is counted: a PF_STRIPS launch moves nothing here;
+// a PF_COMPACT launch, whose level-0 workgroups are the blocks inside the rectangles, counts as 1.)
+static long long g_admission_counts[8] = {};
+void read_admission_counts(long long out[8]) { for (int i = 0; i < 8; i++) out[i] = g_admission_counts[i]; }
+void count_merged_plan() { g_admission_counts[7]++; }
+static void count_admission(const LevelBatch& batch)
+{
+    for (int j = 0; j < batch.njobs; j++) {
+        const LevelJob& J = batch.job[j];
+        if (J.from_warp) {
+            if (j == 0 && batch.tab0_n && batch.need_r0 && J.nrect) g_admission_counts[0]++;
+            else if (J.nrect) g_admission_counts[1]++;
+            else g_admission_counts[2]++;
+            if (!batch.tab0_n) g_admission_counts[3]++;
+        } else if (J.bits_off >= 0) g_admission_counts[4]++;
+        else if (J.nrect) g_admission_counts[5]++;
+        else g_admission_counts[6]++;
+    }
+}
 
 #if PF_EXPERIMENTS
 // The wave-specialised rolling-strip form of the pipelined launch (strips.inc).  Returns false when this launch has to take
@@ -2202,6 +2225,7 @@ void launch_levels(hipStream_t s, const TileLayout& lay, const LevelLaunch* jobs
     }
 #endif
     if (!batch.njobs) return;
+    count_admission(batch);
     FusedWarp w{};
     if (wa) {
         for (int i = 0; i < 9; i++) w.M[i] = wa->M[i];

@@ -226,7 +226,10 @@ static void check_canvas(const Canvas& c)
 
 static void level_plan_checks()
 {
-    struct Shape { int tx, ty, Bc, only_L; } shapes[] = { { 2, 2, 8, 0 }, { 5, 3, 8, 0 }, { 5, 3, 1, 0 }, { 32, 2, 8, 0 }, { 32, 2, 2, 0 }, { 33, 2, 8, 0 }, { 33, 2, 3, 0 }, { 21, 21, 8, 2 }, { 9, 9, 1, 0 } };
+    // (the last seven: the canvases of tests/test_gpu_large_canvas.py, cases A, B, C, D, D', E and the shard pair on A -- the plans the kernel
+    // is run with there)
+    struct Shape { int tx, ty, Bc, only_L; } shapes[] = { { 2, 2, 8, 0 }, { 5, 3, 8, 0 }, { 5, 3, 1, 0 }, { 32, 2, 8, 0 }, { 32, 2, 2, 0 }, { 33, 2, 8, 0 }, { 33, 2, 3, 0 }, { 21, 21, 8, 2 }, { 9, 9, 1, 0 },
+                                                          { 17, 16, 8, 5 }, { 20, 18, 8, 5 }, { 22, 22, 8, 5 }, { 34, 6, 8, 5 }, { 6, 34, 8, 5 }, { 17, 16, 8, 7 }, { 17, 16, 4, 5 } };
     const int Ls[4] = { 1, 2, 5, 7 };
     for (const Shape& s : shapes)
         for (int L : Ls) {
