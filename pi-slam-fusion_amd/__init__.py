@@ -473,6 +473,23 @@ def webtiles_device(dev_ptr, rows, cols, dev_mask, px2ll, zmin=None, zmax=None, 
                                                                  quality, bg, int(pixels), cb, None, stream), pixels)
 
 
+def _image_of(array):
+    """(Image, keepalive) of a host frame as Map2D.feed and Map2D.prepare(images=...) hand it over: the type from the shape -- HxWx3
+    uint8 is PF_8UC3 (BGR), HxWx4 uint8 PF_8UC4 (BGRA as the tracker holds it, TrackerOpt.cpp:376), anything else -1, which the library
+    rejects -- and the row step of a row-padded view (cv::Mat::step) carried over.  No cast: an array of another dtype is not a frame."""
+    img = np.asarray(array)
+    step = 0
+    if img.ndim == 3 and img.dtype == np.uint8 and img.strides[2] == 1 and img.strides[1] == img.shape[2] and img.strides[0] >= img.shape[1] * img.shape[2]:
+        step = img.strides[0]                       # row-padded view: handed over as is
+    else:
+        img = np.ascontiguousarray(img)
+    typ = -1
+    if img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] in (3, 4):
+        typ = PF_8UC3 if img.shape[2] == 3 else PF_8UC4
+    rows, cols = (img.shape[0], img.shape[1]) if img.ndim >= 2 else (0, 0)
+    return Image(rows, cols, typ, img.ctypes.data, step), img
+
+
 def tile_owner(opt, ix, iy):
     return lib().pf_tile_owner(C.byref(opt), ix, iy)
 
@@ -515,8 +532,7 @@ class Map2D:
         if images is not None:
             imgs = (Image * len(images))()
             for i, im in enumerate(images):
-                im = np.ascontiguousarray(im, dtype=np.uint8); keep.append(im)
-                imgs[i] = Image(im.shape[0], im.shape[1], PF_8UC3, im.ctypes.data, 0)
+                imgs[i], k = _image_of(im); keep.append(k)
         return bool(lib().pf_prepare(self._h, ppl, pc, ps.shape[0], imgs, ps.ctypes.data_as(C.POINTER(C.c_double))))
 
     def feed(self, img, pose):
@@ -527,16 +543,7 @@ class Map2D:
         p, pp = _pose(pose)
         if img is None:
             return bool(lib().pf_feed(self._h, None, pp))
-        img = np.asarray(img)
-        step = 0
-        if img.ndim == 3 and img.dtype == np.uint8 and img.strides[2] == 1 and img.strides[1] == img.shape[2] and img.strides[0] >= img.shape[1] * img.shape[2]:
-            step = img.strides[0]                       # row-padded view (cv::Mat::step): handed over as is
-        else:
-            img = np.ascontiguousarray(img)
-        typ = -1
-        if img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] in (3, 4):
-            typ = PF_8UC3 if img.shape[2] == 3 else PF_8UC4      # BGRA as the tracker holds it (TrackerOpt.cpp:376)
-        im = Image(img.shape[0], img.shape[1], typ, img.ctypes.data, step)
+        im, keep = _image_of(img)
         return bool(lib().pf_feed(self._h, C.byref(im), pp))
 
     def feed_device(self, data_ptr, rows, cols, pose, step=0, channels=3):

@@ -359,6 +359,9 @@ void FusionMap::stats(long long* rendered, long long* rejected, long long* dropp
 }
 
 // ---------------------------------------------------------------- prepare
+// the line renderFrame's size / type gate prints (.cpp:319-323)
+static void print_frame_mismatch() { std::fprintf(stderr, "MultiBandMap2DCPU::renderFrame: frame.first.cols!=p->_camera.w||frame.first.rows!=p->_camera.h||frame.first.type()!=CV_8UC3\n"); }
+
 // Map2DPrepare::prepare (Map2D.cpp:32-49) + MultiBandMap2DCPUData::prepare
 // (.cpp:199-255) + MultiBandMap2DCPU::prepare (.cpp:266-286)
 bool FusionMap::prepare(const double plane7[7], const double cam[6], int n, const pf_image* imgs, const double* poses7)
@@ -425,6 +428,8 @@ bool FusionMap::prepare(const double plane7[7], const double cam[6], int n, cons
         // with a render thread the prepare frames are rendered first (Map2D.cpp:42, .cpp:606-615)
         for (int i = 0; i < n; i++) {
             if (!imgs[i].data) continue;
+            // renderFrame's size / type gate (.cpp:319-323), as the threaded feed() applies it: such a frame is never rendered
+            if (frame_mismatch(imgs[i].type, imgs[i].cols, imgs[i].rows)) { print_frame_mismatch(); continue; }
             const int cn = imgs[i].type == PF_8UC4 ? 4 : 3;
             const size_t row_bytes = (size_t)imgs[i].cols * cn, step = imgs[i].step ? imgs[i].step : row_bytes;
             if (step < row_bytes || step * (size_t)imgs[i].rows >= (1ull << 31)) { set_error("prepare: bad row step or frame of 2 GiB or more"); return false; }
@@ -488,9 +493,6 @@ bool FusionMap::upload(const pf_image* img, int slot)
     last_slot_ = slot; last_bytes_ = bytes;
     return true;
 }
-
-// the line renderFrame's size / type gate prints (.cpp:319-323)
-static void print_frame_mismatch() { std::fprintf(stderr, "MultiBandMap2DCPU::renderFrame: frame.first.cols!=p->_camera.w||frame.first.rows!=p->_camera.h||frame.first.type()!=CV_8UC3\n"); }
 
 // MultiBandMap2DCPU::feed (.cpp:288-309)
 bool FusionMap::feed(const pf_image* img, const double pose7[7], bool device_ptr, const FrameProducer* produce)

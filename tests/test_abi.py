@@ -92,6 +92,32 @@ def test_image_type_codes_are_the_reference_headers(pf):
     assert (pf.PF_8UC3, pf.PF_8UC4, pf.PF_16SC3, pf.PF_32FC3) == (types["8UC3"], types["8UC4"], types["16SC3"], types["32FC3"])
 
 
+def test_binding_describes_prepare_images_as_feed_does(pf):
+    """Map2D.feed and Map2D.prepare(images=...) describe a host frame through one helper: the type from the shape (a 4-channel image
+    given to prepare used to be labelled 8UC3 and its first rows * cols * 3 bytes rendered as BGR), the row step of a padded view
+    carried over, no cast of another dtype, and -1 -- which the library rejects -- for what is no frame."""
+    rng = np.random.RandomState(3)
+    bgr = rng.randint(0, 256, (5, 7, 3)).astype(np.uint8)
+    im, keep = pf._image_of(bgr)
+    assert (im.rows, im.cols, im.type, im.step, im.data) == (5, 7, pf.PF_8UC3, 21, bgr.ctypes.data) and keep is bgr
+    bgra = rng.randint(0, 256, (5, 7, 4)).astype(np.uint8)
+    im, keep = pf._image_of(bgra)
+    assert (im.rows, im.cols, im.type, im.step, im.data) == (5, 7, pf.PF_8UC4, 28, bgra.ctypes.data) and keep is bgra
+    wide = rng.randint(0, 256, (5, 9, 4)).astype(np.uint8)
+    view = wide[:, 1:8]                                                   # a ROI of a wider buffer: row step 36, first pixel 4 bytes in
+    im, keep = pf._image_of(view)
+    assert (im.rows, im.cols, im.type, im.step, im.data) == (5, 7, pf.PF_8UC4, 36, wide.ctypes.data + 4) and keep is view
+    for view in (bgra[:, ::2], bgra[::-1]):                                # pixels not side by side / rows backwards: copied, packed
+        im, keep = pf._image_of(view)
+        assert im.type == pf.PF_8UC4 and im.step == 0 and im.data == keep.ctypes.data and np.array_equal(keep, view) and keep.flags["C_CONTIGUOUS"]
+    for other in (bgr.astype(np.float32), bgr.astype(np.int16), bgra.astype(np.uint16)):
+        im, keep = pf._image_of(other)                                    # no silent cast: another dtype is no frame
+        assert im.type == -1 and keep.dtype == other.dtype
+    im, keep = pf._image_of(bgr[:, :, 0])                                 # 2-D: no frame either
+    assert (im.rows, im.cols, im.type) == (5, 7, -1)
+    assert pf._image_of(np.zeros((5, 7, 1), np.uint8))[0].type == -1 and pf._image_of(np.zeros((5, 7, 2), np.uint8))[0].type == -1
+
+
 def test_perspective_transform_same_in_product_and_oracle(pf, orc):
     rng = np.random.RandomState(0)
     for _ in range(50):

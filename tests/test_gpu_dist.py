@@ -251,6 +251,26 @@ def test_dist_seam_exchange_at_cfg2_size(pf, orc, world, force_float):
         d.close()
 
 
+def shards_equal_the_oracle(pf, maps, o, moved, root, nbytes, nframes):
+    """after pf_dist_feed of nframes keyframes of nbytes each from `root` (moved: per rank, the bytes it sent and received): every
+    rank holds the tiles it owns, their union -- tiles and pixels -- is the oracle's map, and whole frames travelled, each at most
+    once per other rank"""
+    from helpers import map_digest
+    world = len(maps)
+    want, got = map_digest(o), {}
+    for r, m in enumerate(maps):
+        for t in m.tiles():
+            assert pf.tile_owner(m.opt, *t) == r
+        d = map_digest(m)
+        assert not (set(d) & set(got))
+        got.update(d)
+        assert m.grid() == o.grid()
+    assert got == want
+    assert moved[root] > 0 and moved[root] % nbytes == 0                      # whole frames left the root ...
+    assert sum(moved) == 2 * moved[root]                                      # ... and every byte sent was received once
+    assert moved[root] <= (world - 1) * nframes * nbytes                      # at most one copy per other rank and frame (ranks without a tile of the canvas get none)
+
+
 @pytest.mark.parametrize("world,force_float,root", [(3, 0, 0), (4, 1, 2)])
 def test_dist_feed_from_one_rank(pf, orc, world, force_float, root):
     """pf_dist_feed: the keyframes live on the host of ONE rank; every rank gets the pose, only the ranks that own a tile
@@ -290,20 +310,7 @@ def test_dist_feed_from_one_rank(pf, orc, world, force_float, root):
     for f, p in zip(frames, poses):
         assert o.feed(f, p)
     out = collective(world, rv, rank_main)
-    from helpers import map_digest
-    want, got = map_digest(o), {}
-    for r, m in enumerate(maps):
-        for t in m.tiles():
-            assert pf.tile_owner(m.opt, *t) == r
-        d = map_digest(m)
-        assert not (set(d) & set(got))
-        got.update(d)
-        assert m.grid() == o.grid()
-    assert got == want
-    nbytes = frames[0].size
-    assert out[root] > 0 and out[root] % nbytes == 0                         # whole frames left the root ...
-    assert sum(out) == 2 * out[root]                                          # ... and every byte sent was received once
-    assert out[root] <= (world - 1) * len(frames) * nbytes                    # at most one copy per other rank and frame (ranks without a tile of the canvas get none)
+    shards_equal_the_oracle(pf, maps, o, out, root, frames[0].size, len(frames))
     for d in dms:
         d.close()
 

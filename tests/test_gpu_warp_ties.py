@@ -39,19 +39,25 @@ PRODUCT = ([{"id": "%s-fused%d" % (t, f), "type": t, "options": {"fused": f}} fo
            + [{"id": "%s-nocull" % t, "type": t, "cull": False} for t in TYPES]
            + [{"id": "%s-lookahead0" % t, "type": t, "options": {"lookahead": 0}} for t in TYPES]
            + [{"id": "%s-nocull-lookahead0" % t, "type": t, "cull": False, "options": {"lookahead": 0}} for t in TYPES]
-           + [{"id": "i16-not-injected", "type": "i16", "inject": False}, {"id": "single-not-injected", "type": "single", "inject": False}])
+           + [{"id": "i16-not-injected", "type": "i16", "inject": False}, {"id": "single-not-injected", "type": "single", "inject": False}]
+           # the same keyframes as BGRA (tests/bgra.py: an alpha plane no colour comes near): cn = 4 in the tap addresses of every level-kernel shape
+           + [{"id": "%s-fused%d-bgra" % (t, f), "type": t, "options": {"fused": f}, "bgra": True} for t in TYPES for f in (1, 3, 2, 0)]
+           + [{"id": "single-bgra", "type": "single", "bgra": True}])
 BOTH = [{"id": t, "type": t} for t in TYPES]
+BOTH_BGRA = [{"id": "%s-bgra" % t, "type": t, "bgra": True} for t in TYPES]
 # experiment forms that change the chain or the taps: (environment, cases, what pf_debug_form_counts must show -- kernels.hip, g_form_counts:
 # 0 block form with the computed weight, 1 with the weight plane, 2 LDS patch, 3 strips; the single-band kernels have no counter)
 VARIANTS = {
     "PF_SEED=1": (BOTH, "c[0] > 0"),
-    "PF_FORCE_GENERAL=1": (BOTH + [{"id": "%s-fused0" % t, "type": t, "options": {"fused": 0}} for t in TYPES] + [{"id": "single", "type": "single"}], "c[0] > 0"),
-    "PF_A_ILP=0": (BOTH, "c[0] > 0"),
+    "PF_FORCE_GENERAL=1": (BOTH + [{"id": "%s-fused0" % t, "type": t, "options": {"fused": 0}} for t in TYPES] + [{"id": "single", "type": "single"}]
+                           + BOTH_BGRA + [{"id": "%s-fused0-bgra" % t, "type": t, "options": {"fused": 0}, "bgra": True} for t in TYPES]
+                           + [{"id": "single-bgra", "type": "single", "bgra": True}], "c[0] > 0"),
+    "PF_A_ILP=0": (BOTH + BOTH_BGRA, "c[0] > 0"),
     "PF_A_ILP=2": (BOTH, "c[0] > 0"),
     "PF_A_ILP=3": (BOTH, "c[0] > 0"),
-    "PF_PATCH=1": (BOTH, "c[2] > 0"),                        # the plan takes the scale-1 keyframes (the shears); the others run the block form
-    "PF_STRIPS=1": (BOTH, "c[3] > 0 and c[0] == 0"),
-    "PF_WEIGHT_PLANE=1": (BOTH, "c[1] > 0 and c[0] == 0"),
+    "PF_PATCH=1": (BOTH + BOTH_BGRA, "c[2] > 0"),                       # the plan takes the scale-1 keyframes (the shears); the others run the block form
+    "PF_STRIPS=1": (BOTH + BOTH_BGRA, "c[3] > 0 and c[0] == 0"),
+    "PF_WEIGHT_PLANE=1": (BOTH + BOTH_BGRA, "c[1] > 0 and c[0] == 0"),
     "PF_SINGLE_OLD=1": ([{"id": "single", "type": "single"}], "True"),
 }
 
@@ -111,7 +117,9 @@ def run_children(models, tmp, exp_lib):
 def results(orc, tmp_path_factory):
     assert os.path.exists(EXP_LIB), "build the experiments library first (__graft_entry__.build())"
     tmp = str(tmp_path_factory.mktemp("warp_ties"))
-    return run_children(build_models(orc, tmp), tmp, EXP_LIB)
+    out = run_children(build_models(orc, tmp), tmp, EXP_LIB)
+    print("\nwarp-ties children, seconds:", {j: round(r[2]["seconds"], 1) for j, r in out.items() if r[2]})
+    return out
 
 
 def case_result(results, job, cid):

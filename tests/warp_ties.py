@@ -238,13 +238,18 @@ def feed_frame(k):
 def run_cases(spec):
     """The child process of tests/test_gpu_warp_ties.py: the library PF_LIB names (the experiments build: the hook exists there alone),
     under the switches of this process' environment.  spec: {"models": {pyramid type: .npz of the model's map}, "cases": [{"id", "type":
-    "i16" | "f32" | "single", "options": pf_options fields, "cull": bool, "inject": bool}]}.  Returns {"forms": pf_debug_form_counts,
-    case id: mismatch strings against the model}."""
+    "i16" | "f32" | "single", "options": pf_options fields, "cull": bool, "inject": bool, "bgra": bool}]}; with "bgra" the keyframes are fed
+    as BGRA, bgra.with_alpha(feed_frame(k), k): the colour content, and so the models, are the same.  Returns {"forms":
+    pf_debug_form_counts, "seconds": what the cases took, case id: mismatch strings against the model}."""
     import ctypes as C
+    import time
+    import bgra
     from conftest import load_package
     from helpers import compare_with_model, workloads
     pf = load_package(); wl = workloads()
     out = {}
+    four = {}                                           # the BGRA keyframes, made once
+    t0 = time.perf_counter()
     for c in spec["cases"]:
         opt = dict(c.get("options", {}))
         if c["type"] == "single":
@@ -257,7 +262,9 @@ def run_cases(spec):
         for k, (name, p) in enumerate(FEEDS):
             if c.get("inject", True):
                 g.next_homography(matrix(name))
-            assert g.feed(feed_frame(k), POSES[p])
+            if c.get("bgra") and k not in four:
+                four[k] = bgra.with_alpha(feed_frame(k), k)
+            assert g.feed(four[k] if c.get("bgra") else feed_frame(k), POSES[p])
         assert g.sync()
         m = StoredMap(spec["models"][c["type"]])
         if c["type"] == "single":
@@ -272,4 +279,5 @@ def run_cases(spec):
         g.close()
     cnt = (C.c_longlong * 8)(); pf.lib().pf_debug_form_counts(cnt)
     out["forms"] = list(cnt)
+    out["seconds"] = time.perf_counter() - t0
     return out
