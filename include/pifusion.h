@@ -429,6 +429,42 @@ size_t  pf_tile_bytes(pf_map* m);
 int     pf_tile_export(pf_map* m, int ix, int iy, void* dev_out);
 int     pf_tile_import(pf_map* m, int ix, int iy, const void* dev_in);
 
+/* --- merging maps, saving and resuming a map's state (no reference counterpart) --------------------
+ * pf_merge: src's tiles merged into dst's on the GPU, by stable tile coordinate.  dst ends, bit for bit, tile by tile and level by
+ * level, as the map that was fed dst's keyframes and then src's: per pixel and level `if (srcW >= dstW) { dstL = srcL; dstW = srcW; }`
+ * (MultiBandMap2DCPU.cpp:521,542 with src as the newer keyframe), for a TypeCPU / TypeGPU map `if (dst.a < src.a) dst = src`
+ * (Map2DCPU.cpp:326); a tile only src holds is copied, one only dst holds is left alone.  Keyframes that still wait in either map are
+ * rendered first; dst's grid grows to hold src's; src is not modified.  Both maps: one device, prepared with the same plane, camera
+ * and poses, the same type, pyramid type, band number and weight type, not sharded -- anything else, or dst == src, returns 0 with
+ * the reason in pf_last_error() and touches nothing.  Keyframes fed to dst afterwards are culled against both maps' weight bounds. */
+int     pf_merge(pf_map* dst, pf_map* src);
+/* the same merge from n slot images the caller holds in m's device memory (what pf_tile_export writes: pf_tile_bytes each, 16-byte
+ * aligned), tile i at stable coordinates (xy[2i], xy[2i+1]): the transport-free primitive for maps of other devices or processes.
+ * wlb16: 16 floats per tile, the exporting map's cull bounds, or NULL when nothing is known of them (entries that are not finite
+ * count as unknown); a coordinate given twice is refused.  The images' content is trusted as pf_tile_import trusts it. */
+int     pf_merge_tiles(pf_map* m, int n, const int* xy, const void* const* dev_slots, const float* wlb16);
+/* the 16 cull bounds of tile (ix, iy), to travel with its pf_tile_export image; 0: the map holds no such tile */
+int     pf_tile_bounds(pf_map* m, int ix, int iy, float wlb16[16]);
+/* The state file: everything a map is -- options that shape its tiles, plane, camera, grid, every tile's pyramid, weights and cull
+ * bounds -- little-endian, a pure function of the state (two saves of one state are the same bytes).  pf_save_state drains and
+ * writes it (on failure no file is left); pf_load_state is "prepare from the file" for a map created with the file's type,
+ * ForceFloat, BandNumber and WeightType (else refused): the old content goes as in a second pf_prepare, and feeding goes on as if
+ * the process had never ended; pf_merge_state merges the file into a prepared map as pf_merge would merge the map that wrote it.
+ * A file that is not what it claims (magic, version, length, slot size, unsorted or duplicate tiles, geometry that is not finite)
+ * is refused with the reason and the map is left as it was; its pixel content is trusted as pf_tile_import trusts a slot. */
+int     pf_save_state(pf_map* m, const char* path);
+int     pf_load_state(pf_map* m, const char* path);
+int     pf_merge_state(pf_map* m, const char* path);
+/* what a state file holds, read by host code alone (no device): info = map type (PF_TYPE_CPU or PF_TYPE_MULTIBAND), pyramid type
+ * (PF_8UC4 / PF_16SC3 / PF_32FC3), band number, weight type, tiles, grid width, grid height in tiles, and the format version of the
+ * file; plane[7], cam[6] as pf_prepare takes them; geo[6] as pf_grid gives it.  Any output may be NULL.  0 for a file pf_load_state
+ * would refuse on sight, with the reason in pf_last_error(). */
+int     pf_state_info(const char* path, int info[8], double plane[7], double cam[6], double geo[6]);
+/* diagnostics of m's most recent merge (tools/merge_rate.py): out = pairs of slots, pairs whose destination had no pyramid, ms
+ * between HIP events around the launches, pixel-levels src won (-1: not counted), bytes of a slot, 0.  count_stores 1 / 0: count
+ * the wins in the merges to come (an atomic per thread: for measuring only) or not; -1: leave the setting. */
+void    pf_debug_merge_stats(pf_map* m, int count_stores, double out[6]);
+
 /* --- the seam exchange inside the library ---------------------------------
  * What a reference-side caller (the Map2DHIP subclass of INTEGRATION.md) needs to run draw() and save() when the mosaic is
  * sharded over the GPUs of a node: one process per GPU, each with its own pf_map created with shard_rank / shard_count,

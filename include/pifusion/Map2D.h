@@ -165,6 +165,12 @@ public:
     bool saveTiff(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
     // the pyramid TIFF with a transparency mask behind every image: covered where the level-0 weight is not 0 (pf_save_tiff_masked)
     bool saveMasked(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff_masked(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
+    // other's tiles merged into this map's on the GPU: this map ends as the map fed its own keyframes and then other's (pf_merge)
+    bool merge(Map2D& other) { return pf_merge(h_, other.h_) != 0; }
+    // the map's whole state in one file, "prepare from the file", and a file merged like a map (pf_save_state / pf_load_state / pf_merge_state)
+    bool saveState(const std::string& filename) { return pf_save_state(h_, filename.c_str()) != 0; }
+    bool loadState(const std::string& filename) { return pf_load_state(h_, filename.c_str()) != 0; }
+    bool mergeState(const std::string& filename) { return pf_merge_state(h_, filename.c_str()) != 0; }
     // north-up Web-Mercator map tiles dir/z/x/y.jpg (+ .pbm coverage of partly covered tiles, tiles.json) around GPS.Origin (pf_save_webtiles);
     // zmax < 0: the native zoom, zmin < 0: down to the zoom at which one tile holds the mosaic
     bool saveWebTiles(const std::string& dir, const double gpsOrigin[3], int zmin = -1, int zmax = -1, int quality = 95)

@@ -169,6 +169,15 @@ def lib():
     L.pf_tile_bytes.argtypes = [vp]; L.pf_tile_bytes.restype = C.c_size_t
     L.pf_tile_export.argtypes = [vp, C.c_int, C.c_int, vp]
     L.pf_tile_import.argtypes = [vp, C.c_int, C.c_int, vp]
+    if hasattr(L, "pf_merge") or not os.environ.get("PF_LIB"):
+        L.pf_merge.argtypes = [vp, vp]
+        L.pf_merge_tiles.argtypes = [vp, C.c_int, ip, C.POINTER(vp), C.POINTER(C.c_float)]
+        L.pf_tile_bounds.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.pf_save_state.argtypes = [vp, C.c_char_p]
+        L.pf_load_state.argtypes = [vp, C.c_char_p]
+        L.pf_merge_state.argtypes = [vp, C.c_char_p]
+        L.pf_state_info.argtypes = [C.c_char_p, ip, dp, dp, dp]
+        L.pf_debug_merge_stats.argtypes = [vp, C.c_int, dp]; L.pf_debug_merge_stats.restype = None
     L.pf_dist_unique_id.argtypes = [vp]
     L.pf_dist_init_rccl.argtypes = [vp, vp, C.c_int, C.c_int]; L.pf_dist_init_rccl.restype = vp
     L.pf_dist_init_host.argtypes = [vp, C.c_int, C.c_int, EXCHANGE_FN, vp]; L.pf_dist_init_host.restype = vp
@@ -490,6 +499,19 @@ def _image_of(array):
     return Image(rows, cols, typ, img.ctypes.data, step), img
 
 
+def state_info(path):
+    """What a map state file holds (pf_state_info; host code, no device): a dict with type, pyramid_type, band_number, weight_type,
+    tiles, w, h (the grid in tiles), version, plane (7), cam (6) and geo (6, as grid() gives it) -- or None, with the reason in
+    pf_last_error(), for a file load_state would refuse on sight."""
+    info = (C.c_int * 8)(); plane = (C.c_double * 7)(); cam = (C.c_double * 6)(); geo = (C.c_double * 6)()
+    if not lib().pf_state_info(os.fsencode(path), info, plane, cam, geo):
+        return None
+    keys = ("type", "pyramid_type", "band_number", "weight_type", "tiles", "w", "h", "version")
+    out = {k: int(v) for k, v in zip(keys, info)}
+    out.update(plane=list(plane), cam=list(cam), geo=list(geo))
+    return out
+
+
 def tile_owner(opt, ix, iy):
     return lib().pf_tile_owner(C.byref(opt), ix, iy)
 
@@ -807,6 +829,48 @@ class Map2D:
 
     def tile_import(self, ix, iy, dev_ptr):
         return bool(lib().pf_tile_import(self._h, ix, iy, dev_ptr))
+
+    # ---- merging maps, saving and resuming a map's state
+    def merge(self, other):
+        """other's tiles merged into this map's on the GPU (pf_merge): this map ends as the map fed its own keyframes and then other's,
+        bit for bit; other is not modified.  False, with the reason in pf_last_error(), for maps that are not compatible."""
+        return bool(lib().pf_merge(self._h, other._h))
+
+    def merge_tiles(self, tiles, dev_ptrs, wlb=None):
+        """pf_merge_tiles: the same merge from slot images in this device's memory (tile_export's; tile_bytes() each, 16-byte aligned),
+        tiles = [(ix, iy)...], dev_ptrs their addresses; wlb: n x 16 float32 cull bounds of the exporting map, None: nothing known."""
+        n = len(tiles)
+        xy = (C.c_int * (2 * max(n, 1)))(*[v for t in tiles for v in t])
+        ptrs = (C.c_void_p * max(n, 1))(*[int(p) for p in dev_ptrs])
+        w = None
+        if wlb is not None:
+            keep = np.ascontiguousarray(wlb, dtype=np.float32).reshape(n, 16)
+            w = keep.ctypes.data_as(C.POINTER(C.c_float))
+        return bool(lib().pf_merge_tiles(self._h, n, xy, ptrs, w))
+
+    def tile_bounds(self, ix, iy):
+        """the 16 cull bounds of a tile (pf_tile_bounds): what merge_tiles takes as wlb beside tile_export's image; None: no such tile"""
+        out = np.empty(16, np.float32)
+        return out if lib().pf_tile_bounds(self._h, ix, iy, out.ctypes.data_as(C.POINTER(C.c_float))) else None
+
+    def save_state(self, path):
+        """the map's whole state into one file (pf_save_state); two saves of one state are the same bytes"""
+        return bool(lib().pf_save_state(self._h, os.fsencode(path)))
+
+    def load_state(self, path):
+        """prepare from a state file (pf_load_state): this map, created with the file's options, becomes the map that wrote it"""
+        return bool(lib().pf_load_state(self._h, os.fsencode(path)))
+
+    def merge_state(self, path):
+        """a state file merged into this prepared map as merge() would merge the map that wrote it (pf_merge_state)"""
+        return bool(lib().pf_merge_state(self._h, os.fsencode(path)))
+
+    def merge_stats(self, count_stores=-1):
+        """diagnostics of the most recent merge (pf_debug_merge_stats): pairs, fresh pairs, ms between HIP events around the launches,
+        pixel-levels the other map won (-1: not counted), slot bytes.  count_stores=True / False switches the counting for later merges."""
+        o = (C.c_double * 6)()
+        lib().pf_debug_merge_stats(self._h, int(count_stores), o)
+        return {"pairs": int(o[0]), "fresh": int(o[1]), "ms": o[2], "won": int(o[3]), "slot_bytes": int(o[4])}
 
     # ---- measurement
     def profile_enable(self, mode=1):

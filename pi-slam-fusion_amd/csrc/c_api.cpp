@@ -2,6 +2,7 @@
 #include "dist.hpp"
 #include "jpeg_device.hpp"
 #include "webtiles_plan.hpp"
+#include "state_file.hpp"
 #include <cerrno>
 #include <map>
 #include <string>
@@ -502,6 +503,30 @@ int pf_blend_tile_halo(pf_map* m, int ix, int iy, const void* const dev_halo[9],
 size_t pf_tile_bytes(pf_map* m) { return m ? m->impl.tile_bytes() : 0; }
 int pf_tile_export(pf_map* m, int ix, int iy, void* dev_out) { return m && dev_out && m->impl.tile_export(ix, iy, dev_out); }
 int pf_tile_import(pf_map* m, int ix, int iy, const void* dev_in) { return m && dev_in && m->impl.tile_import(ix, iy, dev_in); }
+
+// --- map merge, state file (fusion_map.cpp, merge.hip, state_file.hpp)
+int pf_merge(pf_map* dst, pf_map* src)
+{
+    if (!dst || !src) { pf::set_error("pf_merge: null map"); return 0; }
+    return dst->impl.merge_from(src->impl);
+}
+int pf_merge_tiles(pf_map* m, int n, const int* xy, const void* const* dev_slots, const float* wlb16) { return m && m->impl.merge_tiles(n, xy, dev_slots, wlb16); }
+int pf_tile_bounds(pf_map* m, int ix, int iy, float wlb16[16]) { return m && wlb16 && m->impl.tile_bounds(ix, iy, wlb16); }
+int pf_save_state(pf_map* m, const char* path) { return m && path && m->impl.save_state(path); }
+int pf_load_state(pf_map* m, const char* path) { return m && path && m->impl.load_state(path); }
+int pf_merge_state(pf_map* m, const char* path) { return m && path && m->impl.merge_state(path); }
+int pf_state_info(const char* path, int info[8], double plane[7], double cam[6], double geo[6])
+{
+    pf::statefile::StateHeader h; std::string why;
+    if (!pf::statefile::scan_path(path, h, nullptr, why)) { pf::set_error("pf_state_info: " + why); return 0; }
+    if (h.n_tiles > 0x7fffffffull) { pf::set_error("pf_state_info: more tiles than the count can say"); return 0; }
+    if (info) { info[0] = h.map_type; info[1] = h.pyramid_type; info[2] = h.band_number; info[3] = h.weight_type; info[4] = (int)h.n_tiles; info[5] = h.w; info[6] = h.h; info[7] = (int)h.version; }
+    if (plane) std::memcpy(plane, h.plane, sizeof(h.plane));
+    if (cam) std::memcpy(cam, h.cam, sizeof(h.cam));
+    if (geo) { geo[0] = h.min[0]; geo[1] = h.min[1]; geo[2] = h.max[0]; geo[3] = h.max[1]; geo[4] = h.ele_size; geo[5] = h.length_pixel; }
+    return 1;
+}
+void pf_debug_merge_stats(pf_map* m, int count_stores, double out[6]) { if (m) m->impl.merge_stats(count_stores, out); }
 
 // --- seam exchange (dist.cpp)
 struct pf_dist { pf::DistMap impl; pf_map* owner; pf_dist(pf_map* m, pf::Transport* t) : impl(&m->impl, t), owner(m) {} };

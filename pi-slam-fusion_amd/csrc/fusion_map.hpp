@@ -11,8 +11,10 @@
 #include "jpeg_encode.hpp"
 #include "tiff_pyramid.hpp"
 #include "webtiles.hpp"
+#include "merge.hpp"
 #include <hip/hip_runtime.h>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -237,6 +239,22 @@ public:
     size_t tile_bytes() const { return lay_.slot_bytes; }
     bool tile_export(int ix, int iy, void* dev_out);
     bool tile_import(int ix, int iy, const void* dev_in);
+    // Map merge (merge.hpp): src's tiles selected into this map's, by stable tile coordinate -- the map that was fed
+    // this map's keyframes and then src's, bit for bit.  Both maps prepared alike on one device, neither sharded; src is not modified.
+    // Refusals (false, last_error() says why) touch nothing.
+    bool merge_from(FusionMap& src);
+    // ... from n slot images the caller holds in this device's memory (what tile_export writes; 16-byte aligned), at stable coordinates
+    // xy[2n].  wlb16: 16 cull bounds per tile, or null when nothing is known of them (not finite: -1)
+    bool merge_tiles(int n, const int* xy, const void* const* dev_slots, const float* wlb16);
+    bool tile_bounds(int ix, int iy, float wlb16[16]);      // the tile's cull bounds, to travel with tile_export's image
+    // The state file (state_file.hpp): save_state writes this map's whole state; load_state is "prepare from the file" (the map's own
+    // options must be the file's); merge_state merges the file's tiles into this prepared, compatible map as merge_from would
+    bool save_state(const char* path);
+    bool load_state(const char* path);
+    bool merge_state(const char* path);
+    // the most recent merge: pairs, pairs whose dst was fresh, ms between HIP events around its launches, pixel-levels src won (-1: not
+    // counted), slot bytes, 0.  count_stores >= 0 switches the counting (one atomic per thread: measurement only) for the merges to come
+    void merge_stats(int count_stores, double out[6]);
 
     void profile_enable(int mode);
     int  profile_read(int cap, const char** names, double* ms, long long* launches, double* bytes, double* bytes_run = nullptr);
@@ -256,6 +274,7 @@ public:
 private:
     bool render_frame(const QueuedFrame& f);                       // .cpp:311-558
     bool spread_map(double xmin, double ymin, double xmax, double ymax);   // .cpp:561-604
+    void spread_tiles(const Win& r);                               // ... its second half: the grid grown to hold dense tile range r
     // footprint -> bounding box -> spreadMap when it leaves the grid -> tile range r (dense index); box: xmin, ymin, xmax, ymax
     bool canvas_range(const double pts[8], Win& r);
     void tile_range(double xmin, double ymin, double xmax, double ymax, Win& r) const;
@@ -297,6 +316,7 @@ private:
     Camera cam_{};
     double ele_size_ = 0, ele_size_inv_ = 0, length_pixel_ = 0, length_pixel_inv_ = 0;
     double min_[3]{}, max_[3]{};
+    double min0_[3]{};                          // min_ as prepare computed it: the origin of the stable tile coordinates (merge: same frame <=> same min0_, ele_size_)
     int    w_ = 0, h_ = 0, off_x_ = 0, off_y_ = 0;
     TileStore store_;
 
@@ -442,6 +462,19 @@ private:
 #if PF_EXPERIMENTS
     bool blend_batch_per_level(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host);
 #endif
+
+    // map merge / state file
+    struct MergeItem { int ix, iy; const void* src; const float* wlb; };      // wlb: 16 bounds of the src tile, or null
+    bool merge_items(const std::vector<MergeItem>& items);         // mu_ held, drained: tiles created first, one table, launches in batches, flags and bounds
+    bool merge_compatible(const char* who, bool single, int pyr, int bands, int weight_type, const double plane7[7], const double cam6[6],
+                          const double min0[3], double ele_size, double length_pixel);
+    void grow_to(int sx0, int sy0, int sx1, int sy1);              // the grid grown to hold stable tile range [sx0, sx1) x [sy0, sy1)
+    bool merge_records(std::FILE* f, const void* header, const void* heads);      // state_file.hpp's StateHeader / vector<TileHead>
+    void wait_worker_idle();
+    DevBuf merge_table_, merge_stage_, merge_won_;
+    hipEvent_t merge_ev_[2]{};
+    bool   merge_count_ = false;
+    double last_merge_[6] = { 0, 0, 0, -1, 0, 0 };
 
     // frame staging + feed queue
     std::vector<FrameSlot> slots_;
