@@ -465,6 +465,40 @@ int     pf_state_info(const char* path, int info[8], double plane[7], double cam
  * the wins in the merges to come (an atomic per thread: for measuring only) or not; -1: leave the setting. */
 void    pf_debug_merge_stats(pf_map* m, int count_stores, double out[6]);
 
+/* --- Undistortion: frames of a distorted camera ("Undistortion").
+ * The input camera is a GSLAM parameter vector in[n] as Camera::Camera(std::vector<double>) reads it (GSLAM/core/Camera.h:407-416):
+ * n = 6 PinHole (w, h, fx, fy, cx, cy), n = 7 ATAN (..., d), n = 11 OpenCV (..., k1, k2, p1, p2, k3); in[0], in[1] are the input frame's
+ * width and height.  The output camera out6 is a pinhole as pf_prepare takes it; the two sizes may differ.  Every output pixel (x, y) has
+ * one table entry q = in.Project(out.UnProject(x, y)), computed in double as UndistorterImpl::prepareReMap does
+ * (GSLAM/core/Undistorter.h:85-168) and stored as two floats, or (-1, -1) where q lies outside [0, w_in) x [0, h_in): an UNCOVERED
+ * pixel, black in the undistorted frame.  The pixel is Undistorter::undistort's bilinear colour branch, byte for byte, with the taps
+ * clamped into the source.
+ *
+ * pf_undistort_table: the table on the host, no GPU needed: x, y take out_w * out_h floats each (either may be NULL), *uncovered (may be
+ * NULL) the number of uncovered pixels.  pf_undistort_fit_camera: out6 (in: the wanted output camera; out: the fitted one) keeps w, h,
+ * cx, cy and has (fx, fy) multiplied by the smallest s = k / 4096 >= 1 at which every pixel of the output image's four border lines is
+ * covered; 0 when there is none up to s = 64, out6 untouched.  Both return 0 with pf_last_error() for a camera that is not valid. */
+int     pf_undistort_table(const double* in, int n, const double out6[6], float* x, float* y, long long* uncovered);
+int     pf_undistort_fit_camera(const double* in, int n, double out6[6]);
+/* One frame undistorted on the GPU (current device).  src: in[1] rows of in[0] pixels, PF_8UC3 or PF_8UC4 (the alpha byte is ignored),
+ * any row step; dst: out_h rows of out_w packed BGR8 pixels, dst_step bytes apart (0: packed).  pf_undistort_bgr: host to host, complete
+ * when it returns.  pf_undistort_device: src->data and dst are device pointers and the kernel is queued on hip_stream (NULL: the default
+ * stream); the call returns without waiting for it.  The table of the most recent camera pair is kept in device memory, so a run of calls
+ * with one pair builds it once. */
+int     pf_undistort_bgr(const double* in, int n, const double out6[6], const pf_image* src, uint8_t* dst, size_t dst_step);
+int     pf_undistort_device(const double* in, int n, const double out6[6], const pf_image* src, void* dst, size_t dst_step, void* hip_stream);
+/* The map's input camera.  While one is set, every frame that comes in -- pf_feed, pf_feed_device, pf_feed_jpeg(_batch), the frames of
+ * pf_prepare, with or without a render thread -- is a frame of THAT camera and of its size (any other size is rejected as pf_feed rejects
+ * a mismatched frame) and is undistorted on the GPU into the camera of pf_prepare before the map sees it; a pf_feed_device frame is read
+ * by that kernel in stream order, not later.  n = 0 clears it.  It may be set before or after pf_prepare and survives pf_prepare: the
+ * table is built and uploaded as soon as both cameras are known.  pf_load_state clears it (a state file holds the output camera only):
+ * set it again after loading.  n not in {0, 6, 7, 11}, a camera that is not valid or a failed allocation returns 0 with pf_last_error()
+ * and leaves the map as it was.  pf_dist_feed / pf_dist_feed_jpeg refuse a map that has one. */
+int     pf_set_input_camera(pf_map* m, const double* in, int n);
+/* 0: no input camera.  Otherwise the size of the frames the map now expects and the number of uncovered pixels of its table (-1 while
+ * the map is not prepared); any output may be NULL. */
+int     pf_input_camera_info(pf_map* m, int* rows_in, int* cols_in, long long* uncovered);
+
 /* --- the seam exchange inside the library ---------------------------------
  * What a reference-side caller (the Map2DHIP subclass of INTEGRATION.md) needs to run draw() and save() when the mosaic is
  * sharded over the GPUs of a node: one process per GPU, each with its own pf_map created with shard_rank / shard_count,

@@ -126,6 +126,11 @@ public:
         double p[7]; pifusion::pose7(pose, p);
         return pf_feed_jpeg(h_, data, len, p) != 0;
     }
+    // The frames fed from now on are those of a distorted camera -- GSLAM parameters as Camera(std::vector<double>) reads them: 6 PinHole,
+    // 7 ATAN, 11 OpenCV, with their own width and height -- and are undistorted on the GPU into the camera of prepare() before the map
+    // sees them (the reference's dataset adapters call GSLAM::Undistorter for this).  An empty vector clears it.  Survives prepare(),
+    // not loadState().  false: pf_last_error() says why, nothing changed
+    bool setInputCamera(const std::vector<double>& paras) { return pf_set_input_camera(h_, paras.empty() ? nullptr : paras.data(), (int)paras.size()) != 0; }
     // draw(): refresh every tile whose Ischanged flag is set and pass (ix, iy, BGR8 256x256) on.
     // With fuseGoogle() set, `announce` receives what the reference hands to scommand.Call("MapWidget", ...) for every refreshed
     // tile that is not on the rim of the grid (MultiBandMap2DCPU.cpp:744-757): "Map2DUpdate LastTexMat <gpsTL> <gpsBR>".

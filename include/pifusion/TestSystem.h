@@ -222,6 +222,13 @@ inline int testMap2D(const std::string& datapath, const std::vector<std::string>
     if (!map) { std::cerr << "No map2d created!\n"; return -5; }
     const std::vector<double> vecP = svar.GetVec("Camera.Paraments");
     if (vecP.size() != 6) { std::cerr << "Invalid camera parameters!\n"; return -5; }
+    // optional Map2D.InputCamera: the frames are those of a distorted camera (GSLAM parameters, ATAN: 7, OpenCV: 11) and the map
+    // undistorts them into Camera.Paraments.  Absent, nothing changes
+    const std::vector<double> vecIn = svar.GetVec("Map2D.InputCamera");
+    if (!vecIn.empty()) {
+        if (vecIn.size() != 7 && vecIn.size() != 11) { std::cerr << "Invalid input camera parameters!\n"; return -5; }
+        if (!map->setInputCamera(vecIn)) { std::cerr << pf_last_error() << "\n"; return -5; }
+    }
     const std::vector<double> pl = svar.GetVec("Plane");
     const pi::SE3d plane = pl.size() == 7 ? pi::SE3d(pl[0], pl[1], pl[2], pl[3], pl[4], pl[5], pl[6]) : pi::SE3d();
     if (!map->prepare(plane, PinHoleParameters((int)vecP[0], (int)vecP[1], vecP[2], vecP[3], vecP[4], vecP[5]), frames)) return -6;

@@ -178,6 +178,14 @@ def lib():
         L.pf_merge_state.argtypes = [vp, C.c_char_p]
         L.pf_state_info.argtypes = [C.c_char_p, ip, dp, dp, dp]
         L.pf_debug_merge_stats.argtypes = [vp, C.c_int, dp]; L.pf_debug_merge_stats.restype = None
+    if hasattr(L, "pf_set_input_camera") or not os.environ.get("PF_LIB"):
+        fp, llp = C.POINTER(C.c_float), C.POINTER(C.c_longlong)
+        L.pf_undistort_table.argtypes = [dp, C.c_int, dp, fp, fp, llp]
+        L.pf_undistort_fit_camera.argtypes = [dp, C.c_int, dp]
+        L.pf_undistort_bgr.argtypes = [dp, C.c_int, dp, C.POINTER(Image), vp, C.c_size_t]
+        L.pf_undistort_device.argtypes = [dp, C.c_int, dp, C.POINTER(Image), vp, C.c_size_t, vp]
+        L.pf_set_input_camera.argtypes = [vp, dp, C.c_int]
+        L.pf_input_camera_info.argtypes = [vp, ip, ip, llp]
     L.pf_dist_unique_id.argtypes = [vp]
     L.pf_dist_init_rccl.argtypes = [vp, vp, C.c_int, C.c_int]; L.pf_dist_init_rccl.restype = vp
     L.pf_dist_init_host.argtypes = [vp, C.c_int, C.c_int, EXCHANGE_FN, vp]; L.pf_dist_init_host.restype = vp
@@ -516,6 +524,56 @@ def tile_owner(opt, ix, iy):
     return lib().pf_tile_owner(C.byref(opt), ix, iy)
 
 
+# ---- undistortion (pf_undistort_*; DESIGN.md "Undistortion").  camera_in: a GSLAM parameter vector of 6 (PinHole), 7 (ATAN) or 11
+# (OpenCV) numbers; camera_out: the six of a pinhole camera
+def _cameras(camera_in, camera_out):
+    ci = (C.c_double * len(camera_in))(*[float(v) for v in camera_in])
+    co = (C.c_double * 6)(*[float(v) for v in np.asarray(camera_out, dtype=np.float64).reshape(-1)])
+    return ci, co
+
+
+def undistort_table(camera_in, camera_out):
+    """The remap table on the host (no GPU): (x, y, uncovered) -- two float32 arrays of the output camera's h x w, (-1, -1) where the
+    output pixel looks past the input image, and the number of such pixels.  None, with the reason in pf_last_error(), for a camera
+    that is not valid."""
+    ci, co = _cameras(camera_in, camera_out)
+    if not (int(co[0]) >= 1 and int(co[1]) >= 1 and co[0] < 65536 and co[1] < 65536):
+        return None
+    x = np.empty((int(co[1]), int(co[0])), np.float32); y = np.empty_like(x)
+    unc = C.c_longlong(0)
+    fp = C.POINTER(C.c_float)
+    if not lib().pf_undistort_table(ci, len(camera_in), co, x.ctypes.data_as(fp), y.ctypes.data_as(fp), C.byref(unc)):
+        return None
+    return x, y, int(unc.value)
+
+
+def fit_camera(camera_in, camera_out):
+    """camera_out with (fx, fy) multiplied by the smallest s = k / 4096 >= 1 at which the whole border of the output image is covered by
+    the input camera (pf_undistort_fit_camera; host only), as a list of six -- or None when there is none up to s = 64."""
+    ci, co = _cameras(camera_in, camera_out)
+    if not lib().pf_undistort_fit_camera(ci, len(camera_in), co):
+        return None
+    return list(co)
+
+
+def undistort(img, camera_in, camera_out):
+    """One host frame (HxWx3 BGR or HxWx4 BGRA uint8, of camera_in's size) undistorted on the GPU into camera_out: an h x w x 3 array."""
+    ci, co = _cameras(camera_in, camera_out)
+    im, keep = _image_of(img)
+    out = np.empty((max(int(co[1]), 0), max(int(co[0]), 0), 3), np.uint8)
+    if not lib().pf_undistort_bgr(ci, len(camera_in), co, C.byref(im), out.ctypes.data, 0):
+        raise RuntimeError("pf_undistort_bgr failed: %s" % lib().pf_last_error().decode())
+    return out
+
+
+def undistort_device(src_ptr, camera_in, camera_out, dst_ptr, channels=3, src_step=0, dst_step=0, stream=None):
+    """The same on device pointers (pf_undistort_device), queued on `stream`: src_ptr holds camera_in's h rows of w BGR / BGRA pixels,
+    dst_ptr takes camera_out's packed BGR rows."""
+    ci, co = _cameras(camera_in, camera_out)
+    im = Image(int(camera_in[1]), int(camera_in[0]), PF_8UC3 if channels == 3 else PF_8UC4, src_ptr, src_step)
+    return bool(lib().pf_undistort_device(ci, len(camera_in), co, C.byref(im), dst_ptr, dst_step, stream))
+
+
 class Map2D:
     """Map2D::create(type, thread) -> object with prepare/feed/save/queueSize."""
 
@@ -593,6 +651,26 @@ class Map2D:
         res = (C.c_int * n)()
         lib().pf_feed_jpeg_batch(self._h, n, data, lens, pp, threads, res)
         return [bool(r) for r in res]
+
+    # ---- input camera (pf_set_input_camera; DESIGN.md "Undistortion")
+    def set_input_camera(self, camera_in):
+        """From now on every frame fed is a frame of camera_in (GSLAM parameters: 6 PinHole, 7 ATAN, 11 OpenCV; its own width and height)
+        and is undistorted on the GPU into the camera of prepare().  None or () clears it.  Survives prepare(), not load_state()."""
+        vals = [] if camera_in is None else [float(v) for v in camera_in]
+        ci = (C.c_double * max(len(vals), 1))(*vals)
+        return bool(lib().pf_set_input_camera(self._h, ci, len(vals)))
+
+    def input_camera_info(self):
+        """None without an input camera, else (rows_in, cols_in, uncovered): the frame size the map expects and the output pixels the
+        input camera does not cover (-1 before prepare())."""
+        r = C.c_int(0); c = C.c_int(0); u = C.c_longlong(0)
+        if not lib().pf_input_camera_info(self._h, C.byref(r), C.byref(c), C.byref(u)):
+            return None
+        return r.value, c.value, int(u.value)
+
+    undistort = staticmethod(undistort)
+    undistort_table = staticmethod(undistort_table)
+    fit_camera = staticmethod(fit_camera)
 
     def read_last_frame(self):
         """test hook: bytes of the most recently uploaded host frame as they lie in HBM"""

@@ -528,6 +528,118 @@ int pf_state_info(const char* path, int info[8], double plane[7], double cam[6],
 }
 void pf_debug_merge_stats(pf_map* m, int count_stores, double out[6]) { if (m) m->impl.merge_stats(count_stores, out); }
 
+// --- undistortion (undistort_plan.hpp, undistort.hip)
+static bool undistort_cameras(const char* who, const double* in, int n, const double* out6, pf::undistort::InCamera& ic, pf::undistort::OutCamera& oc)
+{
+    if (!pf::undistort::make_camera(in, n, ic)) {
+        pf::set_error(std::string(who) + ": the input camera needs 6 (PinHole), 7 (ATAN) or 11 (OpenCV) finite parameters, w, h >= 1, fx, fy != 0");
+        return false;
+    }
+    if (!pf::undistort::make_out_camera(out6, oc)) { pf::set_error(std::string(who) + ": the output camera needs six finite numbers, w, h >= 1, fx, fy != 0"); return false; }
+    return true;
+}
+int pf_undistort_table(const double* in, int n, const double out6[6], float* x, float* y, long long* uncovered)
+{
+    pf::undistort::InCamera ic; pf::undistort::OutCamera oc;
+    if (!undistort_cameras("pf_undistort_table", in, n, out6, ic, oc)) return 0;
+    const long long u = pf::undistort::build_table(ic, oc, x, y);
+    if (uncovered) *uncovered = u;
+    return 1;
+}
+int pf_undistort_fit_camera(const double* in, int n, double out6[6])
+{
+    pf::undistort::InCamera ic; pf::undistort::OutCamera oc;
+    if (!undistort_cameras("pf_undistort_fit_camera", in, n, out6, ic, oc)) return 0;
+    const int k = pf::undistort::fit_scale(ic, oc);
+    if (!k) { pf::set_error("pf_undistort_fit_camera: no focal length up to 64 times the wanted one has the border covered"); return 0; }
+    const pf::undistort::OutCamera f = pf::undistort::scaled(oc, k);
+    out6[2] = f.fx; out6[3] = f.fy;
+    return 1;
+}
+// the table of the most recent (in, out) pair of pf_undistort_bgr / _device, in the memory of the device it was used on
+static std::mutex g_und_mu;
+static struct { std::vector<double> key; int device = -1; void* table = nullptr; } g_und;
+static const float2* undistort_device_table(const char* who, const double* in, int n, const double* out6, int device, pf::undistort::InCamera& ic, pf::undistort::OutCamera& oc)
+{
+    if (!undistort_cameras(who, in, n, out6, ic, oc)) return nullptr;
+    std::vector<double> key(in, in + n);
+    key.insert(key.end(), out6, out6 + 6);
+    if (g_und.table && g_und.device == device && g_und.key == key) return (const float2*)g_und.table;
+    const size_t pitch = pf::undistort_pitch(oc.w);
+    std::vector<float2> tab(pitch * (size_t)oc.h, float2{ -1.f, -1.f });
+    for (int y = 0; y < oc.h; y++)
+        for (int x = 0; x < oc.w; x++) { float2& e = tab[(size_t)y * pitch + x]; (void)pf::undistort::entry(ic, oc, x, y, e.x, e.y); }
+    if (g_und.table) { (void)hipFree(g_und.table); g_und.table = nullptr; }         // (waits for the kernels that read it)
+    void* p = nullptr;
+    if (hipMalloc(&p, tab.size() * sizeof(float2)) != hipSuccess || hipMemcpy(p, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        pf::set_error(std::string(who) + ": no device memory for the remap table");
+        return nullptr;
+    }
+    g_und.key = key; g_und.device = device; g_und.table = p;
+    return (const float2*)p;
+}
+static bool undistort_source_ok(const char* who, const pf::undistort::InCamera& ic, const pf_image* src, int out_w, size_t& src_step, size_t& dst_step)
+{
+    if (!src || !src->data || (src->type != PF_8UC3 && src->type != PF_8UC4) || src->cols != ic.w || src->rows != ic.h) {
+        pf::set_error(std::string(who) + ": the source is not a BGR8 / BGRA8 frame of the input camera's size"); return false;
+    }
+    const size_t row = (size_t)src->cols * (src->type == PF_8UC4 ? 4 : 3);
+    src_step = src->step ? src->step : row;
+    if (dst_step == 0) dst_step = (size_t)out_w * 3;
+    if (src_step < row || dst_step < (size_t)out_w * 3) { pf::set_error(std::string(who) + ": a row step is smaller than a row"); return false; }
+    return true;
+}
+int pf_undistort_device(const double* in, int n, const double out6[6], const pf_image* src, void* dst, size_t dst_step, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_und_mu);
+    if (!dst) { pf::set_error("pf_undistort_device: no destination"); return 0; }
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dst) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_undistort_device: destination is not device memory"); return 0; }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_undistort_device: hipSetDevice failed"); return 0; }
+    pf::undistort::InCamera ic; pf::undistort::OutCamera oc;
+    size_t src_step = 0;
+    int ok = 0;
+    const float2* table = undistort_device_table("pf_undistort_device", in, n, out6, at.device, ic, oc);
+    if (table && undistort_source_ok("pf_undistort_device", ic, src, oc.w, src_step, dst_step)) {
+        pf::launch_undistort((hipStream_t)hip_stream, (const uint8_t*)src->data, src_step, ic.w, ic.h, src->type == PF_8UC4 ? 4 : 3, table, (uint8_t*)dst, dst_step, oc.w, oc.h);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) pf::set_error(std::string("pf_undistort_device: ") + hipGetErrorString(e));
+        ok = e == hipSuccess;
+    }
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
+int pf_undistort_bgr(const double* in, int n, const double out6[6], const pf_image* src, uint8_t* dst, size_t dst_step)
+{
+    std::lock_guard<std::mutex> l(g_und_mu);
+    if (!dst) { pf::set_error("pf_undistort_bgr: no destination"); return 0; }
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); pf::set_error("pf_undistort_bgr: no HIP device"); return 0; }
+    pf::undistort::InCamera ic; pf::undistort::OutCamera oc;
+    size_t src_step = 0;
+    const float2* table = undistort_device_table("pf_undistort_bgr", in, n, out6, device, ic, oc);
+    if (!table || !undistort_source_ok("pf_undistort_bgr", ic, src, oc.w, src_step, dst_step)) return 0;
+    const int cn = src->type == PF_8UC4 ? 4 : 3;
+    const size_t src_bytes = (size_t)(ic.h - 1) * src_step + (size_t)ic.w * cn, out_row = (size_t)oc.w * 3;
+    uint8_t *dsrc = nullptr, *ddst = nullptr;
+    int ok = hipMalloc((void**)&dsrc, src_bytes) == hipSuccess && hipMalloc((void**)&ddst, out_row * oc.h) == hipSuccess &&
+             hipMemcpy(dsrc, src->data, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        pf::launch_undistort(nullptr, dsrc, src_step, ic.w, ic.h, cn, table, ddst, out_row, oc.w, oc.h);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy2D(dst, dst_step, ddst, out_row, out_row, (size_t)oc.h, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) { pf::set_error(std::string("pf_undistort_bgr: ") + hipGetErrorString(hipGetLastError())); }
+    if (dsrc) (void)hipFree(dsrc);
+    if (ddst) (void)hipFree(ddst);
+    return ok;
+}
+int pf_set_input_camera(pf_map* m, const double* in, int n) { return m && (n == 0 || in) && m->impl.set_input_camera(in, n); }
+int pf_input_camera_info(pf_map* m, int* rows_in, int* cols_in, long long* uncovered) { return m && m->impl.input_camera_info(rows_in, cols_in, uncovered); }
+
 // --- seam exchange (dist.cpp)
 struct pf_dist { pf::DistMap impl; pf_map* owner; pf_dist(pf_map* m, pf::Transport* t) : impl(&m->impl, t), owner(m) {} };
 int pf_dist_unique_id(void* out128) { return out128 && pf::rccl_unique_id(out128); }
@@ -545,10 +657,21 @@ pf_dist* pf_dist_init_host(pf_map* m, int rank, int nranks, pf_exchange_fn fn, v
 }
 void pf_dist_destroy(pf_dist* d) { delete d; }
 int pf_dist_blend_changed(pf_dist* d, int* xy, uint8_t* bgr, int cap) { return (d && xy && bgr && cap >= 0) ? d->impl.blend_changed(xy, bgr, cap) : -1; }
-int pf_dist_feed(pf_dist* d, const pf_image* img, const double pose[7], int root) { return (d && img && pose) ? d->impl.feed(img, pose, root) : -1; }
+// frame distribution moves frames of the map's own camera between the ranks: a map with an input camera is refused, nothing touched
+static bool dist_refuses_input_camera(pf_dist* d, const char* who)
+{
+    if (!d->owner->impl.has_input_camera()) return false;
+    pf::set_error(std::string(who) + ": the map has an input camera (pf_set_input_camera); undistort the frames first, or clear it");
+    return true;
+}
+int pf_dist_feed(pf_dist* d, const pf_image* img, const double pose[7], int root)
+{
+    if (!d || !img || !pose || dist_refuses_input_camera(d, "pf_dist_feed")) return -1;
+    return d->impl.feed(img, pose, root);
+}
 int pf_dist_feed_jpeg(pf_dist* d, const uint8_t* data, size_t len, int rows, int cols, const double pose[7], int root)
 {
-    if (!d || !pose) return -1;
+    if (!d || !pose || dist_refuses_input_camera(d, "pf_dist_feed_jpeg")) return -1;
     pf_image img = { rows, cols, PF_8UC3, nullptr, 0 };
     if (d->impl.rank() != root) return d->impl.feed(&img, pose, root);
     // the root: markers + (where the stream needs it) Huffman here, the rest queued on the map's stream into the staged slot

@@ -247,7 +247,7 @@ FusionMap::~FusionMap()
     if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
     blend_src_.release(); blend_out_raw_.release(); blend_out_bgr_.release(); mosaic_table_.release(); w8_.release(); wmap_.release();
     cover_plane_.release(); cover_bytes_.release();
-    merge_table_.release(); merge_stage_.release(); merge_won_.release();
+    merge_table_.release(); merge_stage_.release(); merge_won_.release(); und_table_.release();
     for (auto e : merge_ev_) if (e) (void)hipEventDestroy(e);
     jpeg_enc_.release(); tiff_dev_.release();
     store_.clear();
@@ -420,6 +420,10 @@ bool FusionMap::prepare(const double plane7[7], const double cam[6], int n, cons
     for (auto& p : pending_) release_slot(p.f);
     pending_.clear();
     HIP_OK(sync_all());
+    // the input camera survives prepare(): its table is built for the new output camera first, while a failure can still leave the map as it was
+    DevBuf und_table; long long und_uncovered = 0;
+    if (und_set_ && !build_undistort_table(und_cam_, c, und_table, &und_uncovered)) return false;
+    if (und_set_) { und_table_.release(); und_table_ = und_table; und_uncovered_ = und_uncovered; }
     store_.clear();
     plane_ = plane; plane_inv_ = pinv; cam_ = c;
     length_pixel_ = length_pixel; length_pixel_inv_ = 1. / length_pixel;
@@ -433,6 +437,14 @@ bool FusionMap::prepare(const double plane7[7], const double cam[6], int n, cons
             if (!imgs[i].data) continue;
             // renderFrame's size / type gate (.cpp:319-323), as the threaded feed() applies it: such a frame is never rendered
             if (frame_mismatch(imgs[i].type, imgs[i].cols, imgs[i].rows)) { print_frame_mismatch(); continue; }
+            if (und_set_) {
+                const int slot = undistort_frame(&imgs[i], false, nullptr);
+                if (slot < 0) return false;
+                std::lock_guard<std::mutex> q(qmu_);
+                slots_[slot].queued = true;
+                queue_.push_back({ slot, nullptr, (long)cam_.w * 3, (int)cam_.h, (int)cam_.w, 3, local[i] });
+                continue;
+            }
             const int cn = imgs[i].type == PF_8UC4 ? 4 : 3;
             const size_t row_bytes = (size_t)imgs[i].cols * cn, step = imgs[i].step ? imgs[i].step : row_bytes;
             if (step < row_bytes || step * (size_t)imgs[i].rows >= (1ull << 31)) { set_error("prepare: bad row step or frame of 2 GiB or more"); return false; }
@@ -497,6 +509,95 @@ bool FusionMap::upload(const pf_image* img, int slot)
     return true;
 }
 
+// ---- input camera (undistort_plan.hpp, undistort.hip)
+// the table of (in, out) as the kernel reads it: rows of undistort_pitch(w) (x, y) pairs.  buf is filled only on success
+bool FusionMap::build_undistort_table(const undistort::InCamera& in, const Camera& out, DevBuf& buf, long long* uncovered)
+{
+    const double out6[6] = { out.w, out.h, out.fx, out.fy, out.cx, out.cy };
+    undistort::OutCamera oc;
+    if (!undistort::make_out_camera(out6, oc)) { set_error("input camera: the map's camera cannot be an output camera"); return false; }
+    const size_t pitch = undistort_pitch(oc.w);
+    std::vector<float2> tab;
+    try { tab.assign(pitch * (size_t)oc.h, float2{ -1.f, -1.f }); } catch (const std::bad_alloc&) { set_error("input camera: no memory for the remap table"); return false; }
+    long long unc = 0;
+    for (int y = 0; y < oc.h; y++)
+        for (int x = 0; x < oc.w; x++) {
+            float2& e = tab[(size_t)y * pitch + x];
+            if (!undistort::entry(in, oc, x, y, e.x, e.y)) unc++;
+        }
+    DevBuf b;
+    if (!b.reserve(tab.size() * sizeof(float2))) { (void)hipGetLastError(); set_error("input camera: hipMalloc of the remap table failed"); return false; }
+    if (hipMemcpy(b.p, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); b.release(); set_error("input camera: upload of the remap table failed"); return false;
+    }
+    buf = b;
+    if (uncovered) *uncovered = unc;
+    return true;
+}
+
+bool FusionMap::set_input_camera(const double* in, int n)
+{
+    if (!init_ok_) { set_error("set_input_camera: no device"); return false; }
+    undistort::InCamera cam;
+    if (n != 0 && !undistort::make_camera(in, n, cam)) {
+        set_error("set_input_camera: needs 6 (PinHole), 7 (ATAN) or 11 (OpenCV) finite parameters of a valid camera (w, h >= 1, fx, fy != 0)");
+        return false;
+    }
+    std::lock_guard<std::mutex> l(mu_);
+    if (!set_device()) return false;
+    DevBuf table; long long unc = 0;
+    if (n != 0 && valid_ && !build_undistort_table(cam, cam_, table, &unc)) return false;
+    // frames that wait (feed queue, lookahead) are undistorted already; the kernels that still read the old table have to finish before it goes
+    if (und_table_.p) { HIP_OK(sync_all()); und_table_.release(); }
+    und_set_ = n != 0; und_cam_ = cam; und_table_ = table; und_uncovered_ = unc;
+    return true;
+}
+
+bool FusionMap::input_camera_info(int* rows_in, int* cols_in, long long* uncovered)
+{
+    std::lock_guard<std::mutex> l(mu_);
+    if (!und_set_) return false;
+    if (rows_in) *rows_in = und_cam_.h;
+    if (cols_in) *cols_in = und_cam_.w;
+    if (uncovered) *uncovered = valid_ ? und_uncovered_ : -1;        // -1: no output camera yet
+    return true;
+}
+
+int FusionMap::undistort_frame(const pf_image* img, bool device_ptr, const FrameProducer* produce)
+{
+    // called with mu_ held, und_set_ && valid_ (so und_table_ is the table of the two cameras), the frame's size and type checked
+    const int cn = img->type == PF_8UC4 ? 4 : 3;
+    const size_t row = (size_t)img->cols * cn, step = (img->data && img->step) ? img->step : row;
+    if (step < row || step * (size_t)img->rows >= (1ull << 31)) { set_error("feed: row step smaller than a row, or frame of 2 GiB or more"); return -1; }
+    const int ow = (int)cam_.w, oh = (int)cam_.h;
+    const size_t ostep = (size_t)ow * 3;
+    if (frame_bytes(oh, ow, (long)ostep, 3) < 8) { set_error("feed: frame smaller than 8 bytes"); return -1; }       // the warp loads 8 bytes per source row
+    if (!und_table_.p) { set_error("feed: the input camera has no table"); return -1; }
+    const uint8_t* raw = device_ptr ? (const uint8_t*)img->data : nullptr;
+    int scratch = -1;
+    // whatever was queued on stream_ for a slot stands between it and its next user
+    auto mark = [this](int s) { if (s >= 0) slots_[s].pending = hipEventRecord(slots_[s].consumed, stream_) == hipSuccess; };
+    if (!device_ptr) {
+        scratch = acquire_slot((size_t)img->rows * step);
+        if (scratch < 0) return -1;
+        if (img->data) { if (!upload(img, scratch)) return -1; }
+        else if (!produce || !(*produce)(slots_[scratch].dev, stream_)) { mark(scratch); return -1; }
+        raw = slots_[scratch].dev;
+        std::lock_guard<std::mutex> q(qmu_);
+        slots_[scratch].queued = true;          // not to be handed out again as the frame's own slot
+    }
+    const int slot = acquire_slot((size_t)oh * ostep);
+    if (scratch >= 0) { std::lock_guard<std::mutex> q(qmu_); slots_[scratch].queued = false; }
+    if (slot < 0) { mark(scratch); return -1; }
+    launch_undistort(stream_, raw, step, und_cam_.w, und_cam_.h, cn, (const float2*)und_table_.p, slots_[slot].dev, ostep, ow, oh);
+    const hipError_t e = hipGetLastError();
+    // the scratch slot is free once the kernel has read it; the frame's slot, should the frame be dropped from the feed queue, once it is written
+    mark(scratch); mark(slot);
+    if (e != hipSuccess) { set_error(std::string("k_undistort: ") + hipGetErrorString(e)); return -1; }
+    if (scratch >= 0 && !slots_[scratch].pending) { set_error("feed: hipEventRecord failed"); return -1; }
+    return slot;
+}
+
 // MultiBandMap2DCPU::feed (.cpp:288-309)
 bool FusionMap::feed(const pf_image* img, const double pose7[7], bool device_ptr, const FrameProducer* produce)
 {
@@ -519,7 +620,13 @@ bool FusionMap::feed(const pf_image* img, const double pose7[7], bool device_ptr
                 if (!thread_) { n_rejected_++; return false; }
                 return true;    // the threaded reference enqueues and fails later on the render thread
             }
-            if (img->data) {
+            if (und_set_ && (img->data || produce)) {
+                // a frame of the input camera: remapped into a slot of its own, and from here on a packed BGR8 host frame of the map's camera
+                if (device_ptr && thread_) { set_error("pf_feed_device needs a thread=0 map"); return false; }
+                f.slot = undistort_frame(img, device_ptr, produce);
+                if (f.slot < 0) return false;
+                f.rows = (int)cam_.h; f.cols = (int)cam_.w; f.cn = 3; f.step = (long)cam_.w * 3;
+            } else if (img->data) {
                 const size_t row_bytes = (size_t)img->cols * f.cn;
                 if ((img->step && img->step < row_bytes) || (img->step ? img->step : row_bytes) * (size_t)img->rows >= (1ull << 31)) {
                     set_error("feed: row step smaller than a row, or frame of 2 GiB or more");
@@ -2502,6 +2609,8 @@ bool FusionMap::load_state(const char* path)
     pending_.clear();
     HIP_OK(sync_all());
     store_.clear();
+    // the file does not carry an input camera (the map is in the output camera's geometry): the caller sets it again
+    und_set_ = false; und_table_.release(); und_uncovered_ = 0;
     plane_ = pose_from7(h.plane); plane_inv_ = inverse(plane_);
     cam_ = Camera{ h.cam[0], h.cam[1], h.cam[2], h.cam[3], h.cam[4], h.cam[5], 1. / h.cam[2], 1. / h.cam[3] };
     length_pixel_ = h.length_pixel; length_pixel_inv_ = 1. / h.length_pixel;

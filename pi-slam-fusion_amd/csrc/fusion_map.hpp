@@ -12,6 +12,8 @@
 #include "tiff_pyramid.hpp"
 #include "webtiles.hpp"
 #include "merge.hpp"
+#include "undistort.hpp"
+#include "undistort_plan.hpp"
 #include <hip/hip_runtime.h>
 #include <condition_variable>
 #include <cstdio>
@@ -123,6 +125,13 @@ public:
     // exactly as a host frame that feed() uploaded
     typedef std::function<bool(void* dev, hipStream_t stream)> FrameProducer;
     bool feed(const pf_image* img, const double pose[7], bool device_ptr, const FrameProducer* produce = nullptr);
+    // The input camera (pf_set_input_camera; DESIGN.md "Undistortion"): while one is set, every frame that comes in is a frame of THAT camera
+    // (GSLAM parameter vector, n = 6, 7 or 11) and is remapped on the GPU into the map's own pinhole camera before anything else sees it.
+    // n = 0 clears it.  It may be set before prepare() and survives prepare(); the table is built and uploaded as soon as both cameras are
+    // known.  false (last_error() says why) leaves the map as it was
+    bool set_input_camera(const double* in, int n);
+    bool input_camera_info(int* rows_in, int* cols_in, long long* uncovered);      // false: none set
+    bool has_input_camera() { std::lock_guard<std::mutex> l(mu_); return und_set_; }
     unsigned queue_size();
     long read_back_last_frame(void* out, size_t cap);
     bool sync();
@@ -278,10 +287,20 @@ private:
     // footprint -> bounding box -> spreadMap when it leaves the grid -> tile range r (dense index); box: xmin, ymin, xmax, ymax
     bool canvas_range(const double pts[8], Win& r);
     void tile_range(double xmin, double ymin, double xmax, double ymax, Win& r) const;
-    bool frame_mismatch(int type, int cols, int rows) const { return (type != PF_8UC3 && type != PF_8UC4) || cols != cam_.w || rows != cam_.h; }
+    // (while an input camera is set, the frames that come in have ITS size)
+    bool frame_mismatch(int type, int cols, int rows) const
+    {
+        if (und_set_) return (type != PF_8UC3 && type != PF_8UC4) || cols != und_cam_.w || rows != und_cam_.h;
+        return (type != PF_8UC3 && type != PF_8UC4) || cols != cam_.w || rows != cam_.h;
+    }
     void worker();                                                 // .cpp:619-635
     int  acquire_slot(size_t bytes);
     bool upload(const pf_image* img, int slot);
+    // The one producer of undistorted frames: the raw frame (host pixels, a caller's device pointer, or what `produce` writes) goes into a
+    // scratch slot -- a device pointer is read where it lies -- and k_undistort writes the frame's own slot on stream_.  Both slots carry a
+    // `consumed` event behind the kernel, like any frame slot.  Returns the frame's slot (packed BGR8 of the map's camera), -1 on failure
+    int  undistort_frame(const pf_image* img, bool device_ptr, const FrameProducer* produce);
+    bool build_undistort_table(const undistort::InCamera& in, const Camera& out, DevBuf& buf, long long* uncovered);
     bool blend_batch(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg = nullptr, int level = 0);
     // bytes: SURVEY 8d's algorithmic bytes of the launch for EVERY tile of the canvas; bytes_run (< 0: the same): those of the part of the
     // canvas its blocks actually process (the cull / a shard leave blocks out) -- the numerator of bench.py's roofline.frac
@@ -475,6 +494,12 @@ private:
     hipEvent_t merge_ev_[2]{};
     bool   merge_count_ = false;
     double last_merge_[6] = { 0, 0, 0, -1, 0, 0 };
+
+    // input camera (guarded by mu_): und_table_ holds the remap table for (und_cam_, cam_) whenever und_set_ && valid_
+    bool und_set_ = false;
+    undistort::InCamera und_cam_{};
+    DevBuf und_table_;
+    long long und_uncovered_ = 0;
 
     // frame staging + feed queue
     std::vector<FrameSlot> slots_;

@@ -46,6 +46,11 @@ class DroneMapDataset:
         self.camera = self.cfg.get("Camera.Paraments")
         if not self.camera or len(self.camera) != 6:
             raise ValueError("Invalid camera parameters!")              # backup/map2dfusion.cpp testMap2D
+        # optional: the frames are those of a distorted camera, GSLAM parameters of an ATAN (7) or OpenCV (11) model, and the map
+        # undistorts them into Camera.Paraments (Map2D.set_input_camera).  Absent: the frames are Camera.Paraments' own
+        self.input_camera = self.cfg.get("Map2D.InputCamera")
+        if self.input_camera is not None and (not isinstance(self.input_camera, list) or len(self.input_camera) not in (7, 11)):
+            raise ValueError("Invalid input camera parameters!")
         self.gps_origin = self.cfg.get("GPS.Origin")
         self.frames = read_trajectory(os.path.join(datapath, "trajectory.txt"))
 

@@ -26,6 +26,8 @@ ds = importlib.import_module("pi_slam_fusion_amd.dataset").DroneMapDataset(a.dat
 dt = importlib.import_module("pi_slam_fusion_amd.datatrans")
 m = pf.Map2D.create(pf.TypeMultiBandCPU, bool(a.thread), force_float=1 if a.float else 0, scale=a.scale)
 n0 = min(a.prepare, len(ds))
+if ds.input_camera is not None:         # Map2D.InputCamera: the frames are a distorted camera's, undistorted by the map
+    assert m.set_input_camera(ds.input_camera), pf.lib().pf_last_error().decode()
 first = [ds.load(k) for k in range(n0)]
 print("Loaded %d frames." % n0)
 assert m.prepare(ds.plane, ds.camera, [p for _, p in first], images=[i for i, _ in first] if a.thread else None)
