@@ -504,7 +504,7 @@ size_t pf_tile_bytes(pf_map* m) { return m ? m->impl.tile_bytes() : 0; }
 int pf_tile_export(pf_map* m, int ix, int iy, void* dev_out) { return m && dev_out && m->impl.tile_export(ix, iy, dev_out); }
 int pf_tile_import(pf_map* m, int ix, int iy, const void* dev_in) { return m && dev_in && m->impl.tile_import(ix, iy, dev_in); }
 
-// --- map merge, state file (fusion_map.cpp, merge.hip, state_file.hpp)
+// --- map merge, state file (map_merge.cpp, merge.hip, state_file.hpp)
 int pf_merge(pf_map* dst, pf_map* src)
 {
     if (!dst || !src) { pf::set_error("pf_merge: null map"); return 0; }

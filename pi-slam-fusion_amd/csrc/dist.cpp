@@ -206,7 +206,7 @@ Transport* make_host_transport(int rank, int nranks, pf_exchange_fn fn, void* us
 
 // ------------------------------------------------------------------ DistMap
 DistMap::DistMap(FusionMap* m, Transport* t) : m_(m), t_(t) { verify_ = std::getenv("PF_DIST_VERIFY") != nullptr; }
-DistMap::~DistMap() { delete t_; send_.release(); recv_.release(); }
+DistMap::~DistMap() { delete t_; }          // (send_ and recv_ free themselves: DevBuf)
 
 // every rank's tile list (coordinates + Ischanged) on every rank: sizes first, then the records
 // (and every rank's cap on the tiles it will blend in this call: the providers must plan with the requester's cap)

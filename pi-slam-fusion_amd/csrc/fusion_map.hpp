@@ -4,6 +4,7 @@
 #include "../../include/pifusion.h"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "map_support.hpp"
 #include "dist_plan.hpp"
 #include "frame_plan.hpp"
 #include "env.hpp"
@@ -29,64 +30,6 @@
 
 namespace pf {
 
-void set_error(const std::string& msg);
-const char* last_error();
-
-// spatial-hash owner of a tile; cells of shard_block tiles
-int tile_owner(int shard_count, int shard_block, int ix, int iy);
-
-// ---- tile store: spatial hash (ix,iy) -> slot in an HBM slab pool ----------
-// replaces the dense vector<SPtr<Ele>> + spreadMap re-layout (.h:91, .cpp:561-604)
-struct Tile {
-    char* base = nullptr;   // slot base in HBM
-    bool  fresh = true;     // pyr_laplace[i].empty() (.cpp:498): first write copies unconditionally
-    bool  changed = false;  // Ele::Ischanged
-    // A lower bound of every weight stored in this tile, all levels (render_frame's cull): each keyframe whose canvas holds the
-    // tile raises it to the smallest weight that keyframe can have anywhere in the cell's pyramid support.  <= 0: nothing known.
-    // Per cell of the cull, row-major: 4 x 4 cells of 64 x 64 pixels (PF_CULL_SUB=2: 2 x 2 quadrants in the first four)
-    float wlb[16] = { -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f };
-};
-
-class TileStore {
-public:
-    ~TileStore() { clear(); }
-    void  configure(size_t slot_bytes) { slot_bytes_ = slot_bytes; }
-    Tile* find(int ix, int iy);
-    Tile* get_or_create(int ix, int iy);          // nullptr on HBM exhaustion
-    bool  reserve(size_t n_tiles, std::vector<std::pair<char*, size_t>>* fresh = nullptr);   // slabs for n more tiles now
-    void  clear();
-    size_t size() const { return map_.size(); }
-    template <class F> void for_each(F f) { for (auto& kv : map_) f((int)(int32_t)(kv.first >> 32), (int)(int32_t)(kv.first & 0xffffffffu), kv.second); }
-#if PF_EXPERIMENTS
-    // test hook (pf_debug_tile_store): from now on get_or_create opens slabs of slab_slots tiles (0: the default size; > 0 also closes the
-    // slab in progress, so that the next new tile opens slab 0), and of the slabs asked for from now on those numbered fail_from ..
-    // fail_from + fail_count - 1 are asked of hipMalloc at 2^60 bytes, which it refuses as it refuses a request the device cannot meet
-    void debug_limits(int slab_slots, int fail_from, int fail_count)
-    {
-        dbg_slab_ = slab_slots > 0 ? (size_t)slab_slots : 0; dbg_no_ = 0; dbg_from_ = fail_from; dbg_count_ = fail_count;
-        if (dbg_slab_ && !chunks_.empty()) next_in_chunk_ = chunks_[cur_].slots;
-    }
-#endif
-private:
-    static uint64_t key(int ix, int iy) { return ((uint64_t)(uint32_t)ix << 32) | (uint32_t)iy; }
-    std::unordered_map<uint64_t, Tile> map_;
-    struct Chunk { char* p; size_t slots; };
-    std::vector<Chunk> chunks_;                   // chunks_[cur_] is being filled, later ones are reserved ahead
-    size_t slot_bytes_ = 0, cur_ = 0, next_in_chunk_ = 0;
-    bool   add_chunk(size_t slots);
-    size_t slab_slots() const;                    // slabs of ~256 MiB: few hipMallocs, tiles of one neighbourhood stay close in HBM
-#if PF_EXPERIMENTS
-    size_t dbg_slab_ = 0; long dbg_no_ = 0, dbg_from_ = 0, dbg_count_ = 0;
-#endif
-};
-
-struct DevBuf {
-    void*  p = nullptr;
-    size_t cap = 0;
-    bool   reserve(size_t bytes);     // grow-only; caller must have synchronised users
-    void   release();
-};
-
 struct FrameSlot {
     uint8_t*   dev = nullptr;
     size_t     cap = 0;
@@ -103,15 +46,6 @@ struct QueuedFrame {
     Pose   pose;            // plane coordinates
     long long seq = -1;     // number of the feed() call that brought it (test hook: render_log)
 };
-
-// Named host sections, after pi::Timer (PIL/src/base/time/Timer.h:43-85: enter / leave, calls, min / max / mean per
-// section) with the reference's own section names (MultiBandMap2DCPU.cpp:476,555,563,602,628-630,722,742); each section is
-// also a roctx range when PF_ROCTX=1 (rocprofv3 --marker-trace shows them next to the kernels).
-enum SectionId { T_FEED = 0, T_RENDER, T_APPLY, T_SPREAD, T_UPDATE_TEXTURE, T_SAVE, T_COUNT };
-const char* section_name(int id);
-struct SectionRec { long long n_calls = 0; double min_t = 0, max_t = 0, total_t = 0; };
-void roctx_push(const char* name);
-void roctx_pop();
 
 class FusionMap {
 public:
@@ -209,9 +143,9 @@ public:
     // has no pyramid, or lies on the rim of the dense grid while HighQualityShow is on
     bool map_update_inputs(int ix, int iy, double plane7[7], double mn[2], double* ele, int* x, int* y);
     // the cull of render_frame (tiles in which a keyframe cannot win the select): see there, and frame_plan.hpp
-    long long culled_tiles() { std::lock_guard<std::mutex> l(mu_); (void)drain(); return n_culled_tiles_; }
-    void set_cull(bool on) { std::lock_guard<std::mutex> l(mu_); (void)drain(); cull_on_ = on; }       // default: on unless PF_CULL=0
-    long long culled_cells() { std::lock_guard<std::mutex> l(mu_); (void)drain(); return n_culled_cells_; }
+    long long culled_tiles() { Drained l(*this); return n_culled_tiles_; }
+    void set_cull(bool on) { Drained l(*this); cull_on_ = on; }       // default: on unless PF_CULL=0
+    long long culled_cells() { Drained l(*this); return n_culled_cells_; }
     // test hook: the feed() calls (0-based, counted since creation) whose keyframes renderFrame accepted, in render order -- with thread = true
     // and a queue that drops, the only way to tell an oracle which keyframes the map really holds; the newest 65536
     int  render_log(long long* out, int cap);
@@ -302,14 +236,21 @@ private:
     int  undistort_frame(const pf_image* img, bool device_ptr, const FrameProducer* produce);
     bool build_undistort_table(const undistort::InCamera& in, const Camera& out, DevBuf& buf, long long* uncovered);
     bool blend_batch(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg = nullptr, int level = 0);
-    // bytes: SURVEY 8d's algorithmic bytes of the launch for EVERY tile of the canvas; bytes_run (< 0: the same): those of the part of the
-    // canvas its blocks actually process (the cull / a shard leave blocks out) -- the numerator of bench.py's roofline.frac
-    void prof_begin(int id, double bytes, hipStream_t st = nullptr, double bytes_run = -1);
-    bool prof_would(int id) const;                                 // will the next prof_begin(id) bracket its launch with events?
+    // the kernel-event profiler (KernelProfiler, map_support.hpp) around a launch; st: the stream it goes to, stream_ when null
+    void prof_begin(int id, double bytes, hipStream_t st = nullptr, double bytes_run = -1) { prof_.begin(id, bytes, st ? st : stream_, bytes_run); }
+    bool prof_would(int id) const { return prof_.would(id); }
     hipError_t sync_all();
-    void prof_end();
-    void prof_harvest();
+    void prof_end() { if (prof_.end()) { (void)sync_all(); prof_.harvest(); } }
     bool set_device();
+    // THE DRAIN RULE: every reader of the map's state -- tiles, flags, counters -- takes mu_ and renders the keyframes that wait in the
+    // lookahead window before it looks (drain()).  That is what makes the lookahead exact (PendingFrame, below): what a caller can observe
+    // after feed() k is the map after keyframes 1 .. k.  A reader holds one of these; a site that takes mu_ and must NOT render what waits
+    // (the debug hooks, profile_enable, the input camera) holds a plain lock_guard and says so.  A drain that fails has counted its
+    // keyframes (keyframe_lost()); the next sync() reports them
+    struct Drained {
+        std::lock_guard<std::mutex> l;
+        explicit Drained(FusionMap& m) : l(m.mu_) { (void)m.drain(); }
+    };
 
     pf_options opt_;
     int        band_num_ = 5;
@@ -345,7 +286,6 @@ private:
     static constexpr int kTableRing = 64;           // tile tables in flight (see retire())
     static constexpr int kLvlRing = 16;
     hipEvent_t  lvl_ev_[kMaxLevels][kLvlRing]{};    // fused = 2/3: level i of the frame in ring slot k has run
-    hipStream_t prof_stream_ = nullptr;
     static constexpr int kUpperStreams = 1;         // streams shared by pyramid levels >= 1
     // Tile tables live in device memory (table_dev_, a ring of kTableRing per-frame tables).  How a frame's table gets
     // there: inside the kernel arguments of the launch that carries the frame's level 0, which stores it to the ring slot
@@ -431,7 +371,7 @@ private:
     bool lookahead_ok() const { return opt_.lookahead > 0 && (single_band_ || (opt_.fused == 1 && band_num_ >= 1)) && cull_on_; }     // wherever the cull runs
     bool render_front();                            // renders pending_.front() and removes it; a failure is counted (keyframe_lost)
     bool render_front_stages();                     // ... its stages 4 onwards
-    bool drain();                                   // ... all of them; mu_ held.  First thing every reader of tiles, flags or counters does
+    bool drain();                                   // ... all of them; mu_ held (the drain rule: Drained, above)
     void release_slot(const QueuedFrame& f);
     bool pre_raise(FrameWork& w, std::vector<Tile*>& tiles);
     // A keyframe that was accepted (its geometry is in, the grid has advanced) and is not in the map, because an allocation or a launch
@@ -464,18 +404,9 @@ private:
     // blend / save scratch (blend_lv_: the per-level form of the experiments library only)
     DevBuf blend_lv_[kMaxLevels], blend_src_, blend_out_raw_, blend_out_bgr_, mosaic_table_, strip_desc_;
     DevBuf cover_plane_, cover_bytes_;          // pf_save_to_memory_mask: the mosaic's coverage as a bit plane (coverage.hip), and as bytes
-    // results on their way to the host: two pinned staging slots, filled on copy_stream_ while the host empties the other one
-    static constexpr size_t kOutSlot = (size_t)32 << 20;
     TiffDevice  tiff_dev_;      // save("x.tif"): level buffers and flags of its own, tiles through jpeg_enc_
     JpegEncoder jpeg_enc_;      // save("x.jpg"), pf_blend_tiles_jpeg: reads blend_out_bgr_ on stream_, buffers of its own
-    struct OutPiece { void* dst; const void* src; size_t bytes; };      // host destination, device source
-    uint8_t*    out_pin_[2]{};
-    hipEvent_t  out_copied_[2]{}, out_ready_ = nullptr;
-    hipStream_t copy_stream_ = nullptr;
-    int         out_threads_ = 1;
-    bool        out_ring_ok_ = false;
-    bool out_ring_init();
-    bool download(const std::vector<OutPiece>& pieces);
+    OutRing     out_ring_;      // results on their way to the host
     bool export_webtiles(const SaveTarget& t, const WebTilesJob& job);                        // blend_out_bgr_ + cover_bytes_ of extent t -> the job's map tiles
     bool save_to_caller(SaveTarget& t, int* rows, int* cols, int* tx0, int* ty0);             // save_mosaic() + the extent handed back
 #if PF_EXPERIMENTS
@@ -511,13 +442,7 @@ private:
     std::thread worker_;
 
     // profile
-    struct ProfRec { int id; hipEvent_t a, b; double bytes, bytes_run; };
-    int prof_mode_ = 0; bool prof_on_ = false;
-    unsigned prof_tick_[K_COUNT]{};
-    std::vector<ProfRec> prof_pending_;
-    std::vector<hipEvent_t> ev_pool_;
-    double prof_ms_[K_COUNT]{}; long long prof_n_[K_COUNT]{}; double prof_bytes_[K_COUNT]{}, prof_bytes_run_[K_COUNT]{};
-    ProfRec prof_cur_{};
+    KernelProfiler prof_;
     SectionRec sections_[T_COUNT];
     std::mutex timer_mu_;
     long long n_rendered_ = 0, n_rejected_ = 0, n_dropped_ = 0, n_with_pixels_ = 0;

@@ -1,5 +1,5 @@
 // state_file.hpp -- the map state file: format, writer pieces and the validating parser.  Pure host code, no HIP: the engine
-// (fusion_map.cpp: save_state / load_state / merge_state), pf_state_info and tests/cpp/state_file_check.cpp include it.
+// (map_merge.cpp: save_state / load_state / merge_state), pf_state_info and tests/cpp/state_file_check.cpp include it.
 //
 // Little-endian, a pure function of the map's state (no time stamp, no pointer, no padding left unset):
 //   header   256 bytes (StateHeader)

@@ -119,7 +119,7 @@ def test_hostile_bgra_frames_every_other_path(pf, kind, force_float, group):
 # ---------------------------------------------------------------- BGRA images given to prepare
 @pytest.mark.parametrize("force_float,layout", [(0, "packed"), (1, "packed"), (0, "pad6"), (1, "pad90")])
 def test_bgra_prepare_images_on_the_render_thread(pf, orc, force_float, layout):
-    """A thread = true map renders the images given to prepare first (fusion_map.cpp, Map2D.cpp:42).  The tracker's keyframes are
+    """A thread = true map renders the images given to prepare first (map_feed.cpp, Map2D.cpp:42).  The tracker's keyframes are
     BGRA: the first three go in through prepare(images=...), packed or as row-padded views, the rest through feed, and the map equals
     the oracle fed all of them as BGR in that order -- tiles and saved mosaic, as test_wire.py::test_live_wire_cfg4 compares.  (The
     binding used to label every prepare image 8UC3: rows * cols * 3 bytes of BGRA rendered as BGR, without an error.)"""

@@ -1,4 +1,4 @@
-"""Keyframe undistortion on the GPU (csrc/undistort.hip, the input camera of fusion_map.cpp) against the numpy model of
+"""Keyframe undistortion on the GPU (csrc/undistort.hip, the input camera of map_feed.cpp) against the numpy model of
 tests/undistort_model.py, byte for byte.
 
 Kernel level: pf_undistort_bgr / pf_undistort_device on the golden cases (data of the reference's own Undistorter.h), on sizes that are
