@@ -397,6 +397,68 @@ int     pf_debug_webtiles_batch(int edge);
  * pf_debug_webtiles_timing_read: their milliseconds in the most recent export and the number of tiles it sampled */
 void    pf_debug_webtiles_timing(int on);
 void    pf_debug_webtiles_timing_read(double out4[4]);
+
+/* --- views: the mosaic at any pan, zoom, rotation or camera pose, rendered on the GPU at the size of the caller's window (DESIGN.md
+ * "Views") ---
+ * S_k: the mosaic at pyramid level k as pf_save_to_memory_level(k) gives it; C_k its coverage, 255 where weights[k] != 0, else 0;
+ * B G R C stacked as a 4-channel 8-bit image.  A view is cv::warpPerspective(S_k as BGRA, M0, Size(width, height), INTER_LINEAR,
+ * BORDER_CONSTANT 0) with OpenCV 2.4.9's arithmetic; after the warp every pixel whose fourth channel is 0 gets bg_color in its three
+ * colour channels; a 3-channel view is the first three channels of that.
+ *
+ * V[9] (row-major) takes plane metres to view pixels, (col, row, 1) ~ V (x, y, 1), in the frame of pf_prepare's plane and pf_grid's
+ * geo: it stays valid when the grid grows.  A level-0 pixel index i lies at origin + i lengthPixel, a level-k index j over level-0
+ * index 2^k j, so for a region whose first tile is (tx, ty)
+ *     A_k = [[lp 2^k, 0, min.x + (tx - off_x) eleSize], [0, lp 2^k, min.y + (ty - off_y) eleSize], [0, 0, 1]],   M0 = V A_k.
+ * level = 0 .. L is taken as given; level = -1 chooses k = clamp(floor(log2(max(s, 1))), 0, L), s the square root of |det| of the
+ * Jacobian of (view pixel -> level-0 pixel) at the view's centre ((width - 1) / 2, (height - 1) / 2).
+ * Only the tiles the view depends on are collapsed (pf_view_info.rect, .tiles): the cost follows the window, not the map; the
+ * result is byte-equal to the warp of the whole mosaic.
+ *
+ * Refused (0, the reason in pf_last_error(), no output touched): a V that is not finite; a singular M0; a denominator that is zero or
+ * changes sign over the view's four corners; width or height outside 1 .. 16384; a region of more than 32767 level-k pixels a side
+ * (ask for a higher level); a TypeCPU / TypeGPU map; a sharded map (shard_count > 1); a map before pf_prepare.  A map without
+ * content, or a view that misses the content, is not an error: bg_color everywhere, coverage 0, info.empty = 1. */
+typedef struct pf_view_info {
+    int    level;        /* the level the view was taken from */
+    int    rect[4];      /* the tiles collapsed: first tile x, y (stable tile coordinates), tiles across, tiles down */
+    int    window[4];    /* the level-k pixels the view can reach, inside rect: x0, y0, width, height */
+    double M0[9];        /* level-k pixel of rect -> view pixel: what cv::warpPerspective is handed */
+    double Minv[9];      /* its inverse by the closed-form adjugate: what the warp runs with */
+    int    empty;        /* 1: no content under the view */
+    int    tiles;        /* rect[2] * rect[3] */
+} pf_view_info;
+/* the plan alone, host code without a device or a map: dims[4], geo[6] as pf_grid gives them, num_levels as pf_num_levels,
+ * extent = {first tile x, y, tiles across, tiles down} of the content (across or down 0: none). */
+int     pf_view_plan(const double V[9], int width, int height, int level, const int dims[4], const double geo[6], int num_levels,
+                     const int extent[4], pf_view_info* out);
+/* The view of the map after every keyframe fed so far (keyframes that wait for the lookahead are rendered first; Ischanged flags are
+ * left alone).  channels: 4 (B G R C) or 3; step: bytes between rows, 0 = packed; info may be NULL.
+ * pf_render_view: into host memory (page-locked memory of pf_host_alloc is filled straight from HBM).
+ * pf_render_view_device: into device memory of the map's device, left in HBM for a tracker; the work is queued on hip_stream when
+ * one is given (the call returns once it is queued), else on the map's stream and complete on return.
+ * pf_render_view_jpeg: the 3-channel view as one JPEG stream, encoded on the GPU -- only the stream crosses to the host; byte-equal
+ * to pf_jpeg_encode_bgr of the 3-channel view.  out = NULL: *len = an upper bound for any content, nothing is rendered; otherwise
+ * *len = the stream's length, and 0 + pf_last_error() when it does not fit cap. */
+int     pf_render_view(pf_map* m, const double V[9], int width, int height, int level, int channels, uint8_t* out, size_t step, pf_view_info* info);
+int     pf_render_view_device(pf_map* m, const double V[9], int width, int height, int level, int channels, void* dev_out, size_t step,
+                              void* hip_stream, pf_view_info* info);
+int     pf_render_view_jpeg(pf_map* m, const double V[9], int width, int height, int level, int quality, uint8_t* out, size_t cap, size_t* len,
+                            pf_view_info* info);
+/* Host-only helpers that make a V.  pf_view_of_extent: the whole content, axes as the map's, aspect kept, centred in width x height
+ * (0: no content).  pf_view_from_pose: what a camera at pose_world7 sees -- cam6 = NULL: the camera of pf_prepare, and the view has
+ * its size --: pf_footprint's four plane points taken to the image corners (0, 0), (w, 0), (0, h), (w, h) by
+ * pf_perspective_transform, as they stand; 0 for a pose pf_feed would reject as oblique.  pf_view_from_lnglat: a north-up window
+ * linear in degrees, (lng_w, lat_n) at the view's corner (0, 0) and (lng_e, lat_s) at (width, height) in web tiles' convention that
+ * continuous coordinate = index + 0.5, through pf_webtiles_georef's chain inverted: a view and the web tiles of one map put a
+ * coordinate on the same mosaic pixel.  (The TIFF's tag calls the extent's corner the corner of pixel 0, half a level-0 pixel from
+ * the convention of the views, where it is the centre of pixel 0: DESIGN.md "Views".) */
+int     pf_view_of_extent(pf_map* m, int width, int height, double V[9]);
+int     pf_view_from_pose(pf_map* m, const double pose_world7[7], const double* cam6_or_null, double V[9]);
+int     pf_view_from_lnglat(pf_map* m, const double gps_origin[3], double lng_w, double lat_n, double lng_e, double lat_s, int width, int height, double V[9]);
+/* measurement hook (tools/view_rate.py): while on, HIP events bracket the collapse, the coverage pass and the view kernel of every
+ * view of m; pf_debug_view_timing_read: their milliseconds in the most recent view and the tiles it collapsed */
+void    pf_debug_view_timing(pf_map* m, int on);
+void    pf_debug_view_timing_read(pf_map* m, double out4[4]);
 /* unused-by-the-reference helpers kept for API completeness (.cpp:57-75)   */
 int     pf_normalize_using_weight_map(const float* weight, float* src3, size_t npix);
 int     pf_mul_weight_map(const float* weight, float* src3, size_t npix);

@@ -210,6 +210,25 @@ public:
         bgr.resize((size_t)rows * cols * 3);
         return pf_save_to_memory_level(h_, level, bgr.data(), &rows, &cols, &tile_x0, &tile_y0) != 0;
     }
+    // draw() at the operator's pan, zoom and rotation, without GL (pf_render_view): the mosaic under V -- row-major 3 x 3, plane metres ->
+    // view pixels -- as height x width x channels bytes, B G R and with channels = 4 the coverage; level -1: the pyramid level the view's
+    // scale chooses.  Rendered on the GPU from the tiles the view depends on.  Returns the image; empty, with the reason in
+    // pf_last_error(), where the view is refused.  info (may be null): the plan
+    std::vector<unsigned char> drawView(const double V[9], int width, int height, int level = -1, int channels = 4, pf_view_info* info = nullptr)
+    {
+        std::vector<unsigned char> image;
+        if (width < 1 || height < 1 || (channels != 3 && channels != 4)) return image;
+        image.resize((size_t)width * height * channels);
+        if (!pf_render_view(h_, V, width, height, level, channels, image.data(), 0, info)) image.clear();
+        return image;
+    }
+    // V of what the camera of prepare() sees at `pose` (camera to world); false for a pose feed() would reject
+    template <class SE3> bool viewFromPose(const SE3& pose, double V[9])
+    {
+        double p[7];
+        pifusion::pose7(pose, p);
+        return pf_view_from_pose(h_, p, nullptr, V) != 0;
+    }
     pf_map* handle() { return h_; }
 
 private:

@@ -67,6 +67,16 @@ class WebTile(C.Structure):
 
 WEBTILE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(WebTile))
 
+
+class ViewInfo(C.Structure):
+    """pf_view_info: the plan of a view (include/pifusion.h)"""
+    _fields_ = [("level", C.c_int), ("rect", C.c_int * 4), ("window", C.c_int * 4), ("M0", C.c_double * 9), ("Minv", C.c_double * 9),
+                ("empty", C.c_int), ("tiles", C.c_int)]
+
+    def as_dict(self):
+        return {"level": self.level, "rect": tuple(self.rect), "window": tuple(self.window), "M0": np.array(self.M0).reshape(3, 3),
+                "Minv": np.array(self.Minv).reshape(3, 3), "empty": bool(self.empty), "tiles": self.tiles}
+
 _lib = None
 
 
@@ -137,6 +147,17 @@ def lib():
         L.pf_debug_webtiles_batch.argtypes = [C.c_int]
         L.pf_debug_webtiles_timing.argtypes = [C.c_int]; L.pf_debug_webtiles_timing.restype = None
         L.pf_debug_webtiles_timing_read.argtypes = [dp]; L.pf_debug_webtiles_timing_read.restype = None
+    if hasattr(L, "pf_view_plan"):
+        vi = C.POINTER(ViewInfo)
+        L.pf_view_plan.argtypes = [dp, C.c_int, C.c_int, C.c_int, ip, dp, C.c_int, ip, vi]
+        L.pf_render_view.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vi]
+        L.pf_render_view_device.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vi]
+        L.pf_render_view_jpeg.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), vi]
+        L.pf_view_of_extent.argtypes = [vp, C.c_int, C.c_int, dp]
+        L.pf_view_from_pose.argtypes = [vp, dp, dp, dp]
+        L.pf_view_from_lnglat.argtypes = [vp, dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, dp]
+        L.pf_debug_view_timing.argtypes = [vp, C.c_int]; L.pf_debug_view_timing.restype = None
+        L.pf_debug_view_timing_read.argtypes = [vp, dp]; L.pf_debug_view_timing_read.restype = None
     L.pf_debug_jpeg_huffman.argtypes = [vp, C.POINTER(C.c_longlong)]; L.pf_debug_jpeg_huffman.restype = None
     L.pf_feed_jpeg_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), dp, C.c_int, ip]
     L.pf_num_levels.argtypes = [vp]
@@ -460,6 +481,23 @@ def webtiles_plan(px2ll, rows, cols, z):
     return tuple(rg), ux, uy, vx, vy
 
 
+def _matrix9(V):
+    a = np.ascontiguousarray(V, dtype=np.float64).reshape(9)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def view_plan(V, width, height, level, dims, geo, num_levels, extent):
+    """pf_view_plan: the plan of a view without a map (host code).  dims, geo as Map2D.grid() gives them, extent = (first tile x, y, tiles
+    across, tiles down) of the content.  Returns the ViewInfo as a dict; raises ValueError with the reason where a view is refused."""
+    _, pv = _matrix9(V)
+    d = (C.c_int * 4)(*[int(v) for v in dims]); e = (C.c_int * 4)(*[int(v) for v in extent])
+    _, g = _d(geo, 6)
+    info = ViewInfo()
+    if not lib().pf_view_plan(pv, int(width), int(height), int(level), d, g, int(num_levels), e, C.byref(info)):
+        raise ValueError(lib().pf_last_error().decode())
+    return info.as_dict()
+
+
 def _collect_webtiles(call, pixels):
     """runs call(sink) and returns the records the sink saw: dicts z, x, y, cover (1 partial, 2 full), jpeg (bytes), mask (256 x 256 bool,
     None for a fully covered tile), and bgr (256 x 256 x 3) when pixels were asked for"""
@@ -774,6 +812,77 @@ class Map2D:
         if not call(out.ctypes.data):
             return None
         return out, (x0.value, y0.value)
+
+    # ---- views (pf_render_view*; DESIGN.md "Views")
+    def render_view(self, V, width, height, level=-1, channels=4, out=None):
+        """The mosaic under V (3 x 3, plane metres -> view pixels) as a height x width x channels uint8 image, warped on the GPU from the
+        tiles the view depends on: B G R and, with channels=4, the coverage.  level=-1: the pyramid level that fits the view's scale.
+        out: a caller's array of that shape (its rows may be padded; host_array(): page-locked, filled straight from HBM).  Returns
+        (array, info dict); raises ValueError with the reason where the view is refused (out keeps its bytes)."""
+        _, pv = _matrix9(V)
+        if out is None:
+            out = np.empty((max(height, 1), max(width, 1), channels), np.uint8)          # (a size the map refuses still gets a buffer to refuse)
+        elif out.dtype != np.uint8 or out.shape != (height, width, channels) or out.strides[2] != 1 or out.strides[1] != channels or out.strides[0] < width * channels:
+            raise ValueError("render_view: out must be height x width x channels uint8 with contiguous pixels")
+        info = ViewInfo()
+        if not lib().pf_render_view(self._h, pv, width, height, level, channels, out.ctypes.data, out.strides[0], C.byref(info)):
+            raise ValueError(lib().pf_last_error().decode())
+        return out, info.as_dict()
+
+    def render_view_device(self, V, width, height, dev_ptr, level=-1, channels=4, step=0, stream=None):
+        """render_view into device memory (e.g. a torch tensor's .data_ptr()): the view stays in HBM.  stream: a hipStream_t handle the
+        work is ordered into (the call returns once it is queued); None: complete on return.  Returns the info dict."""
+        _, pv = _matrix9(V)
+        info = ViewInfo()
+        if not lib().pf_render_view_device(self._h, pv, width, height, level, channels, dev_ptr, step, stream, C.byref(info)):
+            raise ValueError(lib().pf_last_error().decode())
+        return info.as_dict()
+
+    def render_view_jpeg(self, V, width, height, level=-1, quality=95, cap=None):
+        """The 3-channel view as one JPEG stream, encoded on the GPU (only the stream crosses to the host): (bytes, info dict)."""
+        _, pv = _matrix9(V)
+        L = lib(); n = C.c_size_t(0)
+        if cap is None:
+            if not L.pf_render_view_jpeg(self._h, pv, width, height, level, quality, None, 0, C.byref(n), None):
+                raise ValueError(L.pf_last_error().decode())
+            cap = n.value
+        out = np.empty(max(cap, 1), np.uint8)
+        info = ViewInfo()
+        if not L.pf_render_view_jpeg(self._h, pv, width, height, level, quality, out.ctypes.data, cap, C.byref(n), C.byref(info)):
+            raise ValueError(L.pf_last_error().decode())
+        return out[:n.value].tobytes(), info.as_dict()
+
+    def view_of_extent(self, width, height):
+        """V of the whole content fitted into width x height: axes as the map's, aspect kept, centred; None for a map without content"""
+        V = np.zeros(9)
+        return V.reshape(3, 3) if lib().pf_view_of_extent(self._h, width, height, V.ctypes.data_as(C.POINTER(C.c_double))) else None
+
+    def view_from_pose(self, pose_world, camera=None):
+        """V of what a camera at pose_world (7 doubles, camera-to-world) sees; camera: [w h fx fy cx cy], None = the camera of prepare().
+        None for a pose feed() would reject as oblique"""
+        _, pp = _pose(pose_world)
+        pc = None
+        if camera is not None:
+            _, pc = _d(camera, 6)
+        V = np.zeros(9)
+        return V.reshape(3, 3) if lib().pf_view_from_pose(self._h, pp, pc, V.ctypes.data_as(C.POINTER(C.c_double))) else None
+
+    def view_from_lnglat(self, gps_origin, lng_w, lat_n, lng_e, lat_s, width, height):
+        """V of a north-up window linear in degrees, (lng_w, lat_n) at the view's top left corner and (lng_e, lat_s) at its bottom right,
+        placed as webtiles() places the mosaic around gps_origin = (lng, lat, alt)"""
+        _, g = _d(gps_origin, 3)
+        V = np.zeros(9)
+        ok = lib().pf_view_from_lnglat(self._h, g, float(lng_w), float(lat_n), float(lng_e), float(lat_s), width, height, V.ctypes.data_as(C.POINTER(C.c_double)))
+        return V.reshape(3, 3) if ok else None
+
+    def view_timing(self, on=None):
+        """measurement hook: on=True/False switches the HIP events around a view's collapse, coverage pass and view kernel; on=None reads
+        (collapse ms, coverage ms, view kernel ms, tiles collapsed) of the most recent view"""
+        if on is not None:
+            lib().pf_debug_view_timing(self._h, int(on)); return None
+        o = np.zeros(4)
+        lib().pf_debug_view_timing_read(self._h, o.ctypes.data_as(C.POINTER(C.c_double)))
+        return tuple(o)
 
     # ---- Ele surface
     @property

@@ -2,6 +2,7 @@
 #include "dist.hpp"
 #include "jpeg_device.hpp"
 #include "webtiles_plan.hpp"
+#include "view_plan.hpp"
 #include "state_file.hpp"
 #include <cerrno>
 #include <map>
@@ -484,6 +485,47 @@ int pf_save_webtiles(pf_map* m, const char* dir, const double gps_origin[3], int
     if (std::fclose(f) != 0) { pf::set_error("pf_save_webtiles: cannot write " + name); return 0; }
     return 1;
 }
+
+// --- views (view_plan.hpp: the plan, pure host code; view.hip: the kernels; map_view.cpp: the engine)
+int pf_view_plan(const double V[9], int width, int height, int level, const int dims[4], const double geo[6], int num_levels, const int extent[4], pf_view_info* out)
+{
+    const pf::view::PlanResult r = pf::view::plan(V, width, height, level, dims, geo, num_levels, extent, out);
+    if (r != pf::view::kOk) { pf::set_error(std::string("pf_view_plan: ") + pf::view::plan_message(r)); return 0; }
+    return 1;
+}
+int pf_render_view(pf_map* m, const double V[9], int width, int height, int level, int channels, uint8_t* out, size_t step, pf_view_info* info)
+{
+    if (!m || !V || !out) { pf::set_error("pf_render_view: no map, no matrix or no buffer"); return 0; }
+    FusionMap::ViewTarget t;
+    t.kind = FusionMap::ViewTarget::Host; t.out = out; t.step = step; t.channels = channels;
+    return m->impl.render_view(V, width, height, level, t, info);
+}
+int pf_render_view_device(pf_map* m, const double V[9], int width, int height, int level, int channels, void* dev_out, size_t step, void* hip_stream, pf_view_info* info)
+{
+    if (!m || !V || !dev_out) { pf::set_error("pf_render_view_device: no map, no matrix or no buffer"); return 0; }
+    FusionMap::ViewTarget t;
+    t.kind = FusionMap::ViewTarget::Device; t.out = (uint8_t*)dev_out; t.step = step; t.channels = channels;
+    t.stream = (hipStream_t)hip_stream; t.has_stream = hip_stream != nullptr;
+    return m->impl.render_view(V, width, height, level, t, info);
+}
+int pf_render_view_jpeg(pf_map* m, const double V[9], int width, int height, int level, int quality, uint8_t* out, size_t cap, size_t* len, pf_view_info* info)
+{
+    if (!m || !V || !len) { pf::set_error("pf_render_view_jpeg: no map, no matrix or no length"); return 0; }
+    if (!out) {
+        if (width < 1 || width > pf::view::kMaxViewDim || height < 1 || height > pf::view::kMaxViewDim) { pf::set_error(std::string("pf_render_view_jpeg: ") + pf::view::plan_message(pf::view::kSize)); return 0; }
+        *len = pf::jenc::stream_bound(height, width);
+        return 1;
+    }
+    FusionMap::ViewTarget t;
+    t.kind = FusionMap::ViewTarget::Jpeg; t.out = out; t.channels = 3; t.quality = quality; t.cap = cap; t.len = len;
+    return m->impl.render_view(V, width, height, level, t, info);
+}
+int pf_view_of_extent(pf_map* m, int width, int height, double V[9]) { return m && V && m->impl.view_of_extent(width, height, V); }
+int pf_view_from_pose(pf_map* m, const double pose_world7[7], const double* cam6_or_null, double V[9]) { return m && pose_world7 && V && m->impl.view_from_pose(pose_world7, cam6_or_null, V); }
+int pf_view_from_lnglat(pf_map* m, const double gps_origin[3], double lng_w, double lat_n, double lng_e, double lat_s, int width, int height, double V[9])
+{ return m && gps_origin && V && m->impl.view_from_lnglat(gps_origin, lng_w, lat_n, lng_e, lat_s, width, height, V); }
+void pf_debug_view_timing(pf_map* m, int on) { if (m) m->impl.view_timing(on != 0); }
+void pf_debug_view_timing_read(pf_map* m, double out4[4]) { if (m && out4) m->impl.view_timing_read(out4); }
 
 void pf_se3_inverse(const double a[7], double out[7]) { from_pose(pf::inverse(to_pose(a)), out); }
 void pf_se3_mul(const double a[7], const double b[7], double out[7]) { from_pose(pf::mul(to_pose(a), to_pose(b)), out); }

@@ -6,6 +6,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "warp_index.hpp"
+#include "level_step.hpp"
 
 namespace pf {
 namespace cf {
@@ -65,10 +66,8 @@ __device__ __forceinline__ Reg level_region(int k, int level, int Y0, int X0, in
     Reg r{};
     for (int i = k + 1; i <= level; i++) {
         const int rows = rowsk >> (i - k), cols = colsk >> (i - k);
-        ylo = (ylo - 1) >> 1; if (ylo < 0) ylo = 0;
-        xlo = (xlo - 1) >> 1; if (xlo < 0) xlo = 0;
-        yhi = (yhi >> 1) + 1; if (yhi > rows - 1) yhi = rows - 1;
-        xhi = (xhi >> 1) + 1; if (xhi > cols - 1) xhi = cols - 1;
+        level_step(ylo, yhi, rows);
+        level_step(xlo, xhi, cols);
         r.y0 = ylo; r.x0 = xlo; r.h = yhi - ylo + 1; r.w = xhi - xlo + 1; r.poff = poff; r.rows = rows; r.cols = cols;
         poff += r.h * r.w;
     }

@@ -74,6 +74,7 @@ FusionMap::~FusionMap()
         if (i < kMarks && mark_ev_[i]) (void)hipEventDestroy(mark_ev_[i]);
     }
     for (auto e : merge_ev_) if (e) (void)hipEventDestroy(e);
+    for (auto e : view_ev_) if (e) (void)hipEventDestroy(e);
     jpeg_enc_.release(); tiff_dev_.release();
     (void)hipStreamDestroy(stream_);
     // the buffers (DevBuf), the tile store, the output ring and the profiler free what they hold as the members go, after this body: on

@@ -118,6 +118,24 @@ public:
     // multi-band map's tiles are one more device route of save_mosaic(); a single-band map's host mosaic and alpha mask are uploaded
     bool webtiles_georef(const double gps_origin[3], double px2ll[6], int* rows, int* cols);
     bool webtiles(const WebTilesJob& job);
+    // pf_render_view* (map_view.cpp; view_plan.hpp, view.hpp; DESIGN.md "Views"): the map after everything fed so far at any pan, zoom,
+    // rotation or camera pose, at the size of the caller's window; only the tiles the view depends on are collapsed.  Where it goes:
+    struct ViewTarget {
+        enum Kind { Host,        // out: host memory (through the output ring)
+                    Device,      // out: device memory; queued on `stream` when has_stream, else on the map's stream and complete on return
+                    Jpeg };      // the 3-channel view as one JPEG stream in out[0 .. cap), *len its length
+        Kind kind = Host;
+        uint8_t* out = nullptr; size_t step = 0; int channels = 4;
+        hipStream_t stream = nullptr; bool has_stream = false;
+        int quality = 95; size_t cap = 0; size_t* len = nullptr;
+    };
+    bool render_view(const double V[9], int width, int height, int level, const ViewTarget& t, pf_view_info* info);
+    // the helpers that only make a V (host code; they read the grid under mu_ without rendering what waits: geometry is in at admission)
+    bool view_of_extent(int width, int height, double V[9]);
+    bool view_from_pose(const double pose_world7[7], const double* cam6, double V[9]);
+    bool view_from_lnglat(const double gps_origin[3], double lng_w, double lat_n, double lng_e, double lat_s, int width, int height, double V[9]);
+    void view_timing(bool on) { std::lock_guard<std::mutex> l(mu_); view_timing_ = on; }
+    void view_timing_read(double out4[4]) { std::lock_guard<std::mutex> l(mu_); for (int i = 0; i < 4; i++) out4[i] = view_ms_[i]; }
 
     // seam exchange support (dist.cpp)
     using TileRec = pf::TileRec;        // dist_plan.hpp
@@ -425,6 +443,13 @@ private:
     hipEvent_t merge_ev_[2]{};
     bool   merge_count_ = false;
     double last_merge_[6] = { 0, 0, 0, -1, 0, 0 };
+
+    // views (map_view.cpp): the sub-table of the rectangle's tile pointers, the collapsed rectangle (BGR8), its coverage (a byte a
+    // pixel) and the view itself on its way to the host or the encoder
+    DevBuf view_table_, view_bgr_, view_cover_, view_out_;
+    hipEvent_t view_ev_[6]{};                   // [0..3] timing hook (pf_debug_view_timing): around the collapse, the coverage pass and the view kernel; [4], [5]: order against a caller's stream
+    bool   view_timing_ = false;
+    double view_ms_[4] = { 0, 0, 0, 0 };        // ... their milliseconds in the most recent view, and the tiles it collapsed
 
     // input camera (guarded by mu_): und_table_ holds the remap table for (und_cam_, cam_) whenever und_set_ && valid_
     bool und_set_ = false;

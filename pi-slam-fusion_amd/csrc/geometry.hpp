@@ -82,11 +82,14 @@ inline bool footprint(const Camera& c, const Pose& pose, double pts[8])
     return true;
 }
 
-inline void perspective_transform(const float src[8], const float dst[8], double M[9])
+// T = float: the reference's Point2f corners (the feed's canvases); T = double: the same set-up and solve for points that must
+// not be rounded to float first (pf_view_from_pose: plane metres)
+template <class T>
+inline void perspective_transform(const T src[8], const T dst[8], double M[9])
 {
     double a[8][9];
     for (int i = 0; i < 4; i++) {
-        const float sx = src[2 * i], sy = src[2 * i + 1], dx = dst[2 * i], dy = dst[2 * i + 1];
+        const T sx = src[2 * i], sy = src[2 * i + 1], dx = dst[2 * i], dy = dst[2 * i + 1];
         double* r0 = a[i]; double* r1 = a[i + 4];
         r0[0] = r1[3] = sx; r0[1] = r1[4] = sy; r0[2] = r1[5] = 1;
         r0[3] = r0[4] = r0[5] = r1[0] = r1[1] = r1[2] = 0;
