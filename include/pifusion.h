@@ -261,6 +261,42 @@ int     pf_feed_jpeg(pf_map* m, const uint8_t* data, size_t len, const double po
  * the frames are uploaded, finished on the GPU and fed in the order given -- the mosaic is the one n pf_feed_jpeg calls build.
  * results[i] (may be NULL) = what pf_feed_jpeg returns for frame i; returns the number of frames fed.                  */
 int     pf_feed_jpeg_batch(pf_map* m, int n, const uint8_t* const* data, const size_t* len, const double* poses7, int threads, int* results);
+/* --- raw frames: what a hardware video decoder, a machine-vision camera or a thermal camera delivers, converted to BGR8 on the GPU
+ * (DESIGN.md "Raw frames"; no reference counterpart: the reference takes CV_8UC3 alone).  8-bit samples.
+ *   PF_RAW_GREY        plane 0: a byte per pixel; B = G = R = the byte (CV_GRAY2BGR).
+ *   PF_RAW_NV12        plane 0: Y; plane 1: interleaved U, V pairs, one pair per 2 x 2 block of pixels, `cols` bytes a chroma row.
+ *   PF_RAW_NV21        the same with V first.
+ *   PF_RAW_I420        plane 0: Y, plane 1: U, plane 2: V, cols / 2 bytes a chroma row (YV12: hand the two chroma pointers over swapped).
+ *                      The three are cv::cvtColor(CV_YUV2BGR_NV12 / _NV21 / _I420) of OpenCV 2.4.9: BT.601 studio range, 20-bit integer
+ *                      arithmetic, no chroma interpolation.  rows and cols even.
+ *   PF_RAW_BAYER_xxxx  plane 0: the mosaic, a byte per pixel, named by the first two pixels of row 0 (RGGB: R G / G B).  Bilinear: on a red
+ *                      or blue site green = (N + S + W + E + 2) >> 2 and the opposite colour = (NW + NE + SW + SE + 2) >> 2; on a green site
+ *                      the colour of its row neighbours = (W + E + 1) >> 1, of its column neighbours = (N + S + 1) >> 1.  The one-pixel
+ *                      frame takes the value of the nearest interior pixel, out(y, x) = interior(clamp(y, 1, rows - 2), clamp(x, 1,
+ *                      cols - 2)).  At least 3 x 3, odd sizes allowed.  This project's specification: not claimed byte-equal to OpenCV.
+ * rows, cols: of the IMAGE.  plane[k]: separate allocations are fine; step[k]: bytes between the rows of plane k, 0 = packed; planes a
+ * format does not use are NULL.
+ * pf_raw_to_bgr: host to host, no GPU needed.  bgr: rows x cols x 3, bgr_step bytes a row (0 = packed); nothing else is written.
+ * pf_raw_to_bgr_device: planes and dev_bgr are device pointers of one device; the kernel is queued on hip_stream (a hipStream_t, NULL =
+ * the default stream) and the call returns without waiting.  Byte-equal to pf_raw_to_bgr.
+ * Refused (0, the reason in pf_last_error(), nothing written): an unknown format, a missing plane, a step below the row, odd YUV sizes,
+ * Bayer below 3 x 3, a plane or a BGR image of 2 GiB or more.
+ * pf_feed_raw: pf_feed of the BGR8 frame the conversion yields, from host planes: each plane crosses to HBM as it lies (1 or 1.5 bytes a
+ * pixel instead of 3) by one blocking copy and is converted there into the frame's slot, so the planes may be released when the call
+ * returns.  Size check (against the input camera, if one is set: the frame is then converted, then undistorted), rejected / dropped
+ * counting, queue (thread=1), lookahead, cull and the cost of an allocation failure are pf_feed's.
+ * pf_feed_raw_device: the same from planes that already lie in HBM (a decoder's output surface); thread=0 maps only.  The conversion is
+ * queued on the map's stream INSIDE the call, not when the keyframe is rendered: the planes must stay valid and unchanged until that
+ * kernel has run -- until pf_sync, for a caller without a handle on the map's stream.
+ * Not provided: raw frames in pf_prepare's frame list or through pf_dist_feed; BT.709 or full-range matrices; 10 / 12 / 16-bit samples;
+ * any demosaic other than bilinear.                                                                                                  */
+enum { PF_RAW_GREY = 1, PF_RAW_NV12 = 2, PF_RAW_NV21 = 3, PF_RAW_I420 = 4,
+       PF_RAW_BAYER_RGGB = 8, PF_RAW_BAYER_BGGR = 9, PF_RAW_BAYER_GRBG = 10, PF_RAW_BAYER_GBRG = 11 };
+typedef struct pf_raw_frame { int format, rows, cols; const void* plane[3]; size_t step[3]; } pf_raw_frame;
+int     pf_raw_to_bgr(const pf_raw_frame* src, uint8_t* bgr, size_t bgr_step);
+int     pf_raw_to_bgr_device(const pf_raw_frame* src, void* dev_bgr, size_t bgr_step, void* hip_stream);
+int     pf_feed_raw(pf_map* m, const pf_raw_frame* src, const double pose[7]);
+int     pf_feed_raw_device(pf_map* m, const pf_raw_frame* src, const double pose[7]);
 /* save() without the file: whole-mosaic collapse into caller memory.  Call
  * with bgr=NULL to query rows/cols/origin tile.                            */
 int     pf_save_to_memory(pf_map* m, uint8_t* bgr, int* rows, int* cols, int* tile_x0, int* tile_y0);

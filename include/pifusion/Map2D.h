@@ -126,6 +126,13 @@ public:
         double p[7]; pifusion::pose7(pose, p);
         return pf_feed_jpeg(h_, data, len, p) != 0;
     }
+    // feed() of the BGR picture a raw frame converts to -- NV12 / NV21 / I420, grey or Bayer, host planes (pf_feed_raw): the planes cross to
+    // HBM as they are, 1 or 1.5 bytes a pixel, and are converted there; they may be released when the call returns
+    template <class SE3> bool feedRaw(const pf_raw_frame& raw, const SE3& pose)
+    {
+        double p[7]; pifusion::pose7(pose, p);
+        return pf_feed_raw(h_, &raw, p) != 0;
+    }
     // The frames fed from now on are those of a distorted camera -- GSLAM parameters as Camera(std::vector<double>) reads them: 6 PinHole,
     // 7 ATAN, 11 OpenCV, with their own width and height -- and are undistorted on the GPU into the camera of prepare() before the map
     // sees them (the reference's dataset adapters call GSLAM::Undistorter for this).  An empty vector clears it.  Survives prepare(),

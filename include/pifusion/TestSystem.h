@@ -147,8 +147,10 @@ public:
         return true;
     }
     // backup/map2dfusion.cpp:122-135.  With `encoded` given (and no decoder hook), a frame that exists as <name>.jpg is handed over
-    // as the file's bytes (frame.first stays empty) for Map2D::feedJpeg to decode on the GPU.
-    bool obtainFrame(std::pair<OwnedImage, pi::SE3d>& frame, std::vector<unsigned char>* encoded = nullptr)
+    // as the file's bytes (frame.first stays empty) for Map2D::feedJpeg to decode on the GPU.  A frame that exists as <name>.nv12 alone -- a
+    // packed NV12 dump of the size of the camera the frames belong to (Map2D.InputCamera if set, else Camera.Paraments) -- is handed over as
+    // the file's bytes in `raw_nv12` when that is given, for Map2D::feedRaw, and converted on the host (pf_raw_to_bgr) otherwise.
+    bool obtainFrame(std::pair<OwnedImage, pi::SE3d>& frame, std::vector<unsigned char>* encoded = nullptr, std::vector<unsigned char>* raw_nv12 = nullptr)
     {
         std::string line;
         if (!in_ || !std::getline(*in_, line)) return false;
@@ -160,9 +162,11 @@ public:
         const std::string base = datapath + "/rgb/" + name;
         frame.first = OwnedImage();
         if (encoded) encoded->clear();
+        if (raw_nv12) raw_nv12->clear();
         if (encoded && !decoder && read_bytes(base + ".jpg", *encoded)) { /* decoded by the map */ }
         else if (!(decoder ? decoder(base + ".jpg", frame.first) : read_native(base + ".jpg", frame.first)) &&
-                 !read_native(base + ".png", frame.first) && !read_ppm_bgr(base + ".ppm", frame.first)) return false;
+                 !read_native(base + ".png", frame.first) && !read_ppm_bgr(base + ".ppm", frame.first) &&
+                 !read_nv12(base + ".nv12", frame.first, raw_nv12)) return false;
         frame.second = pi::SE3d(p[0], p[1], p[2], p[3], p[4], p[5], p[6]);      // SE3 stream order x y z qx qy qz qw (SE3.h:112-117)
         return true;
     }
@@ -179,6 +183,34 @@ public:
         std::fclose(f);
         if (!ok) out.clear();
         return ok;
+    }
+    // the size of the frames on disk: the input camera's when one is configured, else the map's camera's
+    bool frame_size(int& rows, int& cols) const
+    {
+        std::vector<double> cam = cfg.GetVec("Map2D.InputCamera");
+        if (cam.empty()) cam = cfg.GetVec("Camera.Paraments");
+        if (cam.size() < 2) return false;
+        cols = (int)cam[0]; rows = (int)cam[1];
+        return rows > 0 && cols > 0;
+    }
+    // the NV12 descriptor of a packed file of that size
+    static pf_raw_frame nv12_frame(const unsigned char* bytes, int rows, int cols)
+    {
+        pf_raw_frame f{};
+        f.format = PF_RAW_NV12; f.rows = rows; f.cols = cols;
+        f.plane[0] = bytes; f.plane[1] = bytes + (size_t)rows * (size_t)cols;
+        return f;
+    }
+    bool read_nv12(const std::string& file, OwnedImage& out, std::vector<unsigned char>* raw) const
+    {
+        int rows = 0, cols = 0;
+        std::vector<unsigned char> bytes;
+        if (!frame_size(rows, cols) || (rows & 1) || (cols & 1) || !read_bytes(file, bytes)) return false;
+        if (bytes.size() != (size_t)rows * (size_t)cols * 3 / 2) return false;
+        if (raw) { raw->swap(bytes); return true; }
+        out.create(rows, cols, PF_8UC3);
+        const pf_raw_frame f = nv12_frame(bytes.data(), rows, cols);
+        return pf_raw_to_bgr(&f, out.data, 0) != 0;
     }
     // cv::imread(file) through the library: JPEG (or PPM) -> BGR8
     static bool read_native(const std::string& file, OwnedImage& out)
@@ -239,13 +271,15 @@ inline int testMap2D(const std::string& datapath, const std::vector<std::string>
         const auto period = std::chrono::microseconds(fps > 0 ? 1000000 / fps : 0);
         // .jpg frames go to the map as the file's bytes (decoded on the GPU) unless Map2D.DecodeOnHost=1 asks for the reference's order
         const bool on_device = svar.GetInt("Map2D.DecodeOnHost", 0) == 0;
-        std::vector<unsigned char> encoded;
+        std::vector<unsigned char> encoded, raw;
         for (;;) {                                                     // Map2DFusion.cpp:311-327
             const auto t0 = std::chrono::steady_clock::now();
             if (map->queueSize() < 2) {
                 std::pair<OwnedImage, pi::SE3d> frame;
-                if (!ds.obtainFrame(frame, on_device ? &encoded : nullptr)) break;
+                if (!ds.obtainFrame(frame, on_device ? &encoded : nullptr, on_device ? &raw : nullptr)) break;
+                int rows = 0, cols = 0;
                 if (!encoded.empty()) map->feedJpeg(encoded.data(), encoded.size(), frame.second);
+                else if (!raw.empty() && ds.frame_size(rows, cols)) map->feedRaw(DroneMapDataset::nv12_frame(raw.data(), rows, cols), frame.second);
                 else map->feed(frame.first, frame.second);
                 fed++;
             }

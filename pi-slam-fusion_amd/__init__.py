@@ -19,6 +19,9 @@ ELE_PIXELS = 256
 # Map2D::Map2DType (Map2D.h:83)
 NoType, TypeCPU, TypeGPU, TypeMultiBandCPU, TypeRender = 0, 1, 2, 3, 4
 PF_8UC3, PF_8UC4, PF_16SC3, PF_32FC3 = 16, 24, 19, 21
+# raw frame formats (include/pifusion.h, DESIGN.md "Raw frames"); Bayer formats are named by the first two pixels of row 0
+RAW_GREY, RAW_NV12, RAW_NV21, RAW_I420 = 1, 2, 3, 4
+RAW_BAYER_RGGB, RAW_BAYER_BGGR, RAW_BAYER_GRBG, RAW_BAYER_GBRG = 8, 9, 10, 11
 
 
 def host_array(shape, dtype=np.uint8):
@@ -45,6 +48,11 @@ class Options(C.Structure):
 class Image(C.Structure):
     _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("type", C.c_int), ("data", C.c_void_p),
                 ("step", C.c_size_t)]
+
+
+class RawFrame(C.Structure):
+    """pf_raw_frame: rows, cols of the image; up to three planes with their row steps (0 = packed)"""
+    _fields_ = [("format", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("plane", C.c_void_p * 3), ("step", C.c_size_t * 3)]
 
 
 class DistStats(C.Structure):
@@ -207,6 +215,12 @@ def lib():
         L.pf_undistort_device.argtypes = [dp, C.c_int, dp, C.POINTER(Image), vp, C.c_size_t, vp]
         L.pf_set_input_camera.argtypes = [vp, dp, C.c_int]
         L.pf_input_camera_info.argtypes = [vp, ip, ip, llp]
+    if hasattr(L, "pf_feed_raw") or not os.environ.get("PF_LIB"):
+        rf = C.POINTER(RawFrame)
+        L.pf_raw_to_bgr.argtypes = [rf, vp, C.c_size_t]
+        L.pf_raw_to_bgr_device.argtypes = [rf, vp, C.c_size_t, vp]
+        L.pf_feed_raw.argtypes = [vp, rf, dp]
+        L.pf_feed_raw_device.argtypes = [vp, rf, dp]
     L.pf_dist_unique_id.argtypes = [vp]
     L.pf_dist_init_rccl.argtypes = [vp, vp, C.c_int, C.c_int]; L.pf_dist_init_rccl.restype = vp
     L.pf_dist_init_host.argtypes = [vp, C.c_int, C.c_int, EXCHANGE_FN, vp]; L.pf_dist_init_host.restype = vp
@@ -612,6 +626,88 @@ def undistort_device(src_ptr, camera_in, camera_out, dst_ptr, channels=3, src_st
     return bool(lib().pf_undistort_device(ci, len(camera_in), co, C.byref(im), dst_ptr, dst_step, stream))
 
 
+# ---- raw frames (pf_raw_*; DESIGN.md "Raw frames")
+def _raw_planes(planes, format, rows, cols):
+    """(list of 2-D uint8 arrays with contiguous rows, rows, cols) from one array in the usual packed layout (NV12 / NV21: rows * 3 / 2 x cols,
+    I420: the same bytes, Y then U then V; grey and Bayer: rows x cols) or from a tuple of planes (any row stride)."""
+    n = 3 if format == RAW_I420 else 2 if format in (RAW_NV12, RAW_NV21) else 1
+    if isinstance(planes, np.ndarray):
+        a = np.ascontiguousarray(planes, dtype=np.uint8)
+        if n == 1:
+            if a.ndim != 2:
+                raise ValueError("raw frame: a grey or Bayer frame is a rows x cols array")
+            planes = (a,)
+        else:
+            if cols is None:
+                if a.ndim != 2:
+                    raise ValueError("raw frame: a packed YUV frame is a (rows * 3 / 2) x cols array, or give rows and cols")
+                cols = a.shape[1]
+            if rows is None:
+                rows = a.size // cols * 2 // 3
+            if rows < 0 or cols < 0 or rows % 2 or cols % 2 or a.size != rows * cols * 3 // 2:
+                raise ValueError("raw frame: a packed YUV 4:2:0 frame has even rows and cols and rows * cols * 3 / 2 bytes")
+            flat = a.reshape(-1)
+            y = flat[:rows * cols].reshape(rows, cols)
+            if n == 2:
+                planes = (y, flat[rows * cols:].reshape(rows // 2, cols))
+            else:
+                q = rows * cols // 4
+                planes = (y, flat[rows * cols:rows * cols + q].reshape(rows // 2, cols // 2), flat[rows * cols + q:].reshape(rows // 2, cols // 2))
+    planes = list(planes)
+    if len(planes) != n:
+        raise ValueError("raw frame: format %d has %d plane(s)" % (format, n))
+    out = []
+    for p in planes:
+        p = np.asarray(p)
+        if p.dtype != np.uint8 or p.ndim != 2:
+            raise ValueError("raw frame: planes are 2-D uint8 arrays")
+        if p.shape[1] > 1 and p.strides[1] != 1 or (p.shape[0] > 1 and p.strides[0] < p.shape[1]):
+            p = np.ascontiguousarray(p)
+        out.append(p)
+    if rows is None:
+        rows = out[0].shape[0]
+    if cols is None:
+        cols = out[0].shape[1]
+    return out, int(rows), int(cols)
+
+
+def _raw_frame(planes, format, rows, cols):
+    f = RawFrame(int(format), rows, cols)
+    for k, p in enumerate(planes):
+        f.plane[k] = p.ctypes.data
+        f.step[k] = p.strides[0] if p.shape[0] > 1 else p.shape[1]
+    return f
+
+
+class RawImage:
+    """A raw frame on its way to Map2D.feed (the file driver's <name>.nv12): planes as raw_to_bgr takes them, and the RAW_* format."""
+
+    def __init__(self, planes, format, rows=None, cols=None):
+        self.planes, self.format, self.rows, self.cols = planes, format, rows, cols
+
+    def to_bgr(self):
+        return raw_to_bgr(self.planes, self.format, self.rows, self.cols)
+
+
+def raw_to_bgr(planes, format, rows=None, cols=None):
+    """A raw frame (one packed array or a tuple of planes; RAW_* format) converted on the host (pf_raw_to_bgr, no GPU): rows x cols x 3 BGR."""
+    ps, rows, cols = _raw_planes(planes, format, rows, cols)
+    f = _raw_frame(ps, format, rows, cols)
+    out = np.empty((max(rows, 0), max(cols, 0), 3), np.uint8)
+    if not lib().pf_raw_to_bgr(C.byref(f), out.ctypes.data, 0):
+        raise ValueError("pf_raw_to_bgr: %s" % lib().pf_last_error().decode())
+    return out
+
+
+def raw_to_bgr_device(ptrs, steps, format, rows, cols, dst_ptr, dst_step=0, stream=None):
+    """The same on device pointers (pf_raw_to_bgr_device), queued on `stream`: ptrs / steps of the format's planes, dst_ptr takes BGR rows."""
+    f = RawFrame(int(format), int(rows), int(cols))
+    for k, (p, s) in enumerate(zip(ptrs, steps)):
+        f.plane[k] = p
+        f.step[k] = s
+    return bool(lib().pf_raw_to_bgr_device(C.byref(f), dst_ptr, dst_step, stream))
+
+
 class Map2D:
     """Map2D::create(type, thread) -> object with prepare/feed/save/queueSize."""
 
@@ -655,9 +751,11 @@ class Map2D:
 
     def feed(self, img, pose):
         """img: HxWx3 (BGR) or HxWx4 (BGRA) uint8 numpy array (host), None for a geometry-only frame, or the bytes of a .jpg
-        file (decoded by the map: feed_jpeg)."""
+        file (decoded by the map: feed_jpeg), or a RawImage (converted by the map: feed_raw)."""
         if isinstance(img, (bytes, bytearray, memoryview)):
             return self.feed_jpeg(img, pose)
+        if isinstance(img, RawImage):
+            return self.feed_raw(img.planes, img.format, pose, img.rows, img.cols)
         p, pp = _pose(pose)
         if img is None:
             return bool(lib().pf_feed(self._h, None, pp))
@@ -678,6 +776,24 @@ class Map2D:
         p, pp = _pose(pose)
         b = bytes(data)
         return bool(lib().pf_feed_jpeg(self._h, b, len(b), pp))
+
+    def feed_raw(self, planes, format, pose, rows=None, cols=None):
+        """feed() of the BGR picture a raw frame converts to (pf_feed_raw): the planes cross to HBM as they are -- 1 or 1.5 bytes a pixel --
+        and are converted there.  planes: one contiguous array in the usual packed layout (NV12: rows * 3 / 2 x cols) or a tuple of planes."""
+        ps, rows, cols = _raw_planes(planes, format, rows, cols)
+        f = _raw_frame(ps, format, rows, cols)
+        p, pp = _pose(pose)
+        return bool(lib().pf_feed_raw(self._h, C.byref(f), pp))
+
+    def feed_raw_device(self, ptrs, steps, format, rows, cols, pose):
+        """The same from planes that lie in HBM (pf_feed_raw_device; thread=False maps): converted on the map's stream inside the call; the
+        planes must stay valid and unchanged until sync()."""
+        f = RawFrame(int(format), int(rows), int(cols))
+        for k, (q, s) in enumerate(zip(ptrs, steps)):
+            f.plane[k] = q
+            f.step[k] = s
+        p, pp = _pose(pose)
+        return bool(lib().pf_feed_raw_device(self._h, C.byref(f), pp))
 
     def feed_jpeg_batch(self, streams, poses, threads=0):
         """n .jpg keyframes at once: Huffman passes on `threads` host threads (0: one per frame), the rest on the GPU, fed in order.

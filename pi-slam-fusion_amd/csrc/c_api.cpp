@@ -1,6 +1,7 @@
 // c_api.cpp -- extern "C" surface of libpifusion.so (include/pifusion.h).
 #include "dist.hpp"
 #include "jpeg_device.hpp"
+#include "raw_convert.hpp"
 #include "webtiles_plan.hpp"
 #include "view_plan.hpp"
 #include "state_file.hpp"
@@ -569,6 +570,32 @@ int pf_state_info(const char* path, int info[8], double plane[7], double cam[6],
     return 1;
 }
 void pf_debug_merge_stats(pf_map* m, int count_stores, double out[6]) { if (m) m->impl.merge_stats(count_stores, out); }
+
+// --- raw frames (raw_convert.hpp, raw_convert.hip)
+// pf_raw_to_bgr: image_io.cpp (host code without a HIP dependency)
+int pf_raw_to_bgr_device(const pf_raw_frame* src, void* dev_bgr, size_t bgr_step, void* hip_stream)
+{
+    std::string why;
+    if (!src || !dev_bgr) { pf::set_error("pf_raw_to_bgr_device: no frame or no destination"); return 0; }
+    if (!pf::raw::check(*src, why) || !pf::raw::check_bgr(*src, bgr_step, why)) { pf::set_error("pf_raw_to_bgr_device: " + why); return 0; }
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dev_bgr) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_raw_to_bgr_device: destination is not device memory"); return 0; }
+    const int device = at.device;
+    for (int k = 0; k < pf::raw::planes_of(src->format); k++)
+        if (hipPointerGetAttributes(&at, src->plane[k]) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+            (void)hipGetLastError(); pf::set_error("pf_raw_to_bgr_device: plane " + std::to_string(k) + " is not memory of the destination's device"); return 0;
+        }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (device != prev && hipSetDevice(device) != hipSuccess) { pf::set_error("pf_raw_to_bgr_device: hipSetDevice failed"); return 0; }
+    pf::launch_raw_convert((hipStream_t)hip_stream, *src, (uint8_t*)dev_bgr, bgr_step);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) pf::set_error(std::string("pf_raw_to_bgr_device: ") + hipGetErrorString(e));
+    if (device != prev) (void)hipSetDevice(prev);
+    return e == hipSuccess;
+}
+int pf_feed_raw(pf_map* m, const pf_raw_frame* src, const double pose[7]) { return m && m->impl.feed_raw(src, pose, false); }
+int pf_feed_raw_device(pf_map* m, const pf_raw_frame* src, const double pose[7]) { return m && m->impl.feed_raw(src, pose, true); }
 
 // --- undistortion (undistort_plan.hpp, undistort.hip)
 static bool undistort_cameras(const char* who, const double* in, int n, const double* out6, pf::undistort::InCamera& ic, pf::undistort::OutCamera& oc)

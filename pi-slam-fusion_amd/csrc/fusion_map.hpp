@@ -59,6 +59,9 @@ public:
     // exactly as a host frame that feed() uploaded
     typedef std::function<bool(void* dev, hipStream_t stream)> FrameProducer;
     bool feed(const pf_image* img, const double pose[7], bool device_ptr, const FrameProducer* produce = nullptr);
+    // pf_feed_raw / pf_feed_raw_device (raw_convert.hpp; DESIGN.md "Raw frames"): feed() of the BGR8 frame the conversion yields, with a
+    // producer that gets the planes into HBM (host planes: a blocking copy each, into a scratch slot) and converts them into the frame's slot
+    bool feed_raw(const pf_raw_frame* src, const double pose[7], bool device_planes);
     // The input camera (pf_set_input_camera; DESIGN.md "Undistortion"): while one is set, every frame that comes in is a frame of THAT camera
     // (GSLAM parameter vector, n = 6, 7 or 11) and is remapped on the GPU into the map's own pinhole camera before anything else sees it.
     // n = 0 clears it.  It may be set before prepare() and survives prepare(); the table is built and uploaded as soon as both cameras are
@@ -252,6 +255,7 @@ private:
     // scratch slot -- a device pointer is read where it lies -- and k_undistort writes the frame's own slot on stream_.  Both slots carry a
     // `consumed` event behind the kernel, like any frame slot.  Returns the frame's slot (packed BGR8 of the map's camera), -1 on failure
     int  undistort_frame(const pf_image* img, bool device_ptr, const FrameProducer* produce);
+    bool produce_raw(const pf_raw_frame& src, bool device_planes, uint8_t* dst, hipStream_t st);          // called with mu_ held, by feed()
     bool build_undistort_table(const undistort::InCamera& in, const Camera& out, DevBuf& buf, long long* uncovered);
     bool blend_batch(const std::vector<std::pair<int,int>>& tiles, const void* const* halo9, void* raw_host, uint8_t* bgr_host, TileJpeg* jpeg = nullptr, int level = 0);
     // the kernel-event profiler (KernelProfiler, map_support.hpp) around a launch; st: the stream it goes to, stream_ when null

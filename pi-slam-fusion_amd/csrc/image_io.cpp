@@ -8,6 +8,7 @@
 #include "jpeg_decode.hpp"
 #include "jpeg_encode.hpp"
 #include "tiff_pyramid.hpp"
+#include "raw_convert.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -248,6 +249,15 @@ int pf_read_image(const char* filename, uint8_t* bgr, int rows, int cols)
     if (!pf::read_image_file(filename, px, &r, &c)) return 0;
     if (r != rows || c != cols) { pf::set_error("pf_read_image: the buffer does not have the image's size"); return 0; }
     std::memcpy(bgr, px.data(), px.size());
+    return 1;
+}
+// a raw frame converted on the host (raw_convert.hpp): what pf_raw_to_bgr_device and the raw feeds do on the GPU
+int pf_raw_to_bgr(const pf_raw_frame* src, uint8_t* bgr, size_t bgr_step)
+{
+    std::string why;
+    if (!src || !bgr) { pf::set_error("pf_raw_to_bgr: no frame or no destination"); return 0; }
+    if (!pf::raw::check(*src, why) || !pf::raw::check_bgr(*src, bgr_step, why)) { pf::set_error("pf_raw_to_bgr: " + why); return 0; }
+    pf::raw::to_bgr_host(*src, bgr, bgr_step);
     return 1;
 }
 }  // extern "C"

@@ -3,6 +3,7 @@
 #include "fusion_map.hpp"
 #include "map_internal.hpp"
 #include "warp_index.hpp"
+#include "raw_convert.hpp"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -245,6 +246,51 @@ int FusionMap::undistort_frame(const pf_image* img, bool device_ptr, const Frame
     if (e != hipSuccess) { set_error(std::string("k_undistort: ") + hipGetErrorString(e)); return -1; }
     if (scratch >= 0 && !slots_[scratch].pending) { set_error("feed: hipEventRecord failed"); return -1; }
     return slot;
+}
+
+// ---- raw frames (raw_convert.hpp, raw_convert.hip): a front end in the line of pf_feed_jpeg and the input camera
+// The producer of a raw keyframe.  dst: the slot feed() or undistort_frame() acquired for the BGR8 picture.  Host planes go, as they lie,
+// into one scratch slot by a blocking copy each -- the caller may release them when the feed returns -- and the kernel reads them there.
+bool FusionMap::produce_raw(const pf_raw_frame& src, bool device_planes, uint8_t* dst, hipStream_t st)
+{
+    pf_raw_frame dev = src;
+    int scratch = -1;
+    if (!device_planes) {
+        const int np = raw::planes_of(src.format);
+        size_t off[3] = { 0, 0, 0 }, total = 0;
+        for (int k = 0; k < np; k++) { off[k] = total; total += (raw::plane_bytes(src, k) + 255) & ~(size_t)255; }
+        // dst's slot is acquired but neither queued nor pending yet: held, so that it is not handed out a second time as the scratch slot
+        int own = -1;
+        for (size_t i = 0; i < slots_.size(); i++) if (slots_[i].dev == dst) own = (int)i;
+        if (own >= 0) { std::lock_guard<std::mutex> q(qmu_); slots_[own].queued = true; }
+        scratch = acquire_slot(total);
+        if (own >= 0) { std::lock_guard<std::mutex> q(qmu_); slots_[own].queued = false; }
+        if (scratch < 0) return false;
+        for (int k = 0; k < np; k++) {
+            HIP_OK(hipMemcpy(slots_[scratch].dev + off[k], src.plane[k], raw::plane_bytes(src, k), hipMemcpyHostToDevice));
+            dev.plane[k] = slots_[scratch].dev + off[k];
+        }
+    }
+    launch_raw_convert(st, dev, dst, (size_t)src.cols * 3);
+    const hipError_t e = hipGetLastError();
+    // the scratch slot's next blocking upload has to wait for the kernel that reads it
+    if (scratch >= 0) slots_[scratch].pending = hipEventRecord(slots_[scratch].consumed, st) == hipSuccess;
+    if (e != hipSuccess) { set_error(std::string("raw conversion: ") + hipGetErrorString(e)); return false; }
+    if (scratch >= 0 && !slots_[scratch].pending) { set_error("feed: hipEventRecord failed"); return false; }
+    return true;
+}
+
+bool FusionMap::feed_raw(const pf_raw_frame* src, const double pose7[7], bool device_planes)
+{
+    const char* who = device_planes ? "pf_feed_raw_device: " : "pf_feed_raw: ";
+    std::string why;
+    if (!src || !pose7) { set_error(std::string(who) + "no frame or no pose"); return false; }
+    if (!raw::check(*src, why)) { set_error(who + why); return false; }
+    if (device_planes && thread_) { set_error("pf_feed_raw_device needs a thread=0 map"); return false; }
+    // from here on a BGR8 frame of the raw frame's size whose pixels the producer writes: size gate, counters, queue, lookahead as feed() has them
+    const pf_image desc{ src->rows, src->cols, PF_8UC3, nullptr, 0 };
+    const FrameProducer fill = [this, src, device_planes](void* dev, hipStream_t st) { return produce_raw(*src, device_planes, (uint8_t*)dev, st); };
+    return feed(&desc, pose7, false, &fill);
 }
 
 // MultiBandMap2DCPU::feed (.cpp:288-309)

@@ -5,6 +5,9 @@
                             `Camera.Paraments = [w h fx fy cx cy]`, `GPS.Origin = lon lat alt`
     <dir>/trajectory.txt    one keyframe per line: `name x y z qx qy qz qw`
     <dir>/rgb/<name>.jpg    the frames (BGR after decode, as cv::imread gives them)
+
+Beside .jpg, .png and .ppm a frame may be <name>.nv12: a packed NV12 dump of a video decoder (rows of Y, then rows / 2 rows of
+interleaved U, V) of the size of the camera the frames belong to (Map2D.InputCamera if set, else Camera.Paraments).
 """
 import os
 import re
@@ -59,15 +62,25 @@ class DroneMapDataset:
 
     def load(self, k, encoded=False):
         """(BGR uint8 image, pose7) of keyframe k.  encoded=True: a .jpg frame comes back as the file's bytes, for Map2D.feed to decode
-        on the GPU (pf_feed_jpeg)."""
+        on the GPU (pf_feed_jpeg), and a .nv12 frame as a RawImage, for Map2D.feed to convert there (pf_feed_raw); otherwise a .nv12
+        frame is converted on the host (pf_raw_to_bgr)."""
         name, pose = self.frames[k]
         base = os.path.join(self.path, "rgb", name)
         if encoded and os.path.exists(base + ".jpg"):
             return open(base + ".jpg", "rb").read(), pose
-        for ext in (".jpg", ".png", ".ppm", ".npy"):
+        for ext in (".jpg", ".png", ".ppm", ".npy", ".nv12"):
             if os.path.exists(base + ext):
                 if ext == ".npy":
                     return np.load(base + ext), pose
+                if ext == ".nv12":
+                    from . import RAW_NV12, RawImage
+                    cam = self.input_camera if self.input_camera is not None else self.camera
+                    cols, rows = int(cam[0]), int(cam[1])
+                    data = np.fromfile(base + ext, np.uint8)
+                    if rows % 2 or cols % 2 or data.size != rows * cols * 3 // 2:
+                        raise ValueError("%s: not a packed NV12 frame of %d x %d" % (base + ext, cols, rows))
+                    raw = RawImage(data.reshape(rows * 3 // 2, cols), RAW_NV12, rows, cols)
+                    return (raw if encoded else raw.to_bgr()), pose
                 from . import read_image                                   # the library's own readers (csrc/jpeg_decode.cpp, png_decode.cpp)
                 return read_image(base + ext), pose
         raise FileNotFoundError(base + ".jpg")
