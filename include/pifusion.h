@@ -223,6 +223,60 @@ int     pf_tiff_write_bgr_masked(const char* filename, const uint8_t* bgr, int r
 int     pf_tiff_write_device_masked(const char* filename, const void* dev_bgr, int rows, int cols, size_t step,
                                     const void* dev_mask, size_t mask_step, int quality, int bg,
                                     const double model_transform[16], int force_bigtiff, void* hip_stream);
+/* The lossless tile codec (csrc/deflate_rle.hpp, the format's one definition): a tile of 256 x 256 BGR pixels (`step` bytes per
+ * row, 0 = packed) as one complete zlib stream that any inflater reads.
+ *   bytes    N = 196 608 predicted bytes: RGB order, 768 a row; TIFF Predictor 2: pixel 0 of a row as it is, every later sample
+ *            minus the same channel of the pixel before it, mod 256.
+ *   stream   78 01 | 16 deflate blocks, joined bit by bit as RFC 1951 has it | zero bits up to a byte | Adler-32 of the N
+ *            predicted bytes, big-endian.
+ *   blocks   block b covers rows 16 b .. 16 b + 15 = 12 288 bytes; only block 15 has BFINAL.  A block is dynamic (BTYPE 2) when its
+ *            bits (header, tokens, end-of-block) are no more than those of storing it (BTYPE 0) at the bit it begins at: 3 bits,
+ *            zero bits up to a byte, LEN, NLEN, the bytes; else it is stored.  No stream is longer than N + 5 * 16 + 6 bytes.
+ *   tokens   distance 1 only.  A maximal run of equal bytes inside a block: its first byte is a literal -- unless the run begins
+ *            the block, the block is not the tile's first and the last byte of the block before has the run's value: then no
+ *            literal is taken.  Of the R bytes that remain: matches of 258 while R >= 258, then one match of the rest if it is
+ *            >= 3, else literals.  No token spans two blocks.  Length 258 is code 285.
+ *   codes    literal / length code: lengths from the block's counts, end-of-block counted once, by the length builder below with
+ *            limit 15.  Distance code: two codes of length 1 (HDIST = 1); distance 1 is code 0, the bit 0.  HLIT = max(257, last
+ *            used symbol + 1) - 257.  The HLIT + 257 lengths and the distance code's {1, 1} are run-length coded as ONE sequence,
+ *            greedily: a run of r zeros: 18 (up to 138) while r >= 11, then 17 if r >= 3, then single zeros; a run of r equal
+ *            lengths v > 0: v, then 16 (up to 6) while what remains is >= 3, then v for each that remains.  The code-length code:
+ *            the builder with limit 7 on the counts of those symbols; HCLEN drops trailing zeros of the order 16 17 18 0 8 7 9 6
+ *            10 5 11 4 12 3 13 2 14 1 15, never below 4.  Canonical codes as RFC 1951 3.2.2.
+ *   builder  pf_deflate_code_lengths(freq, n, max_len, out), 2 <= n <= 288, max_len <= 15, 2^max_len >= n: a count of 0 gives
+ *            length 0.  One used symbol: it gets length 1, and so does symbol 0 (symbol 1 if the used one is 0).  Else: the
+ *            used symbols sorted by (count, index) ascending; a Huffman tree by two queues (the sorted leaves; the inner nodes in
+ *            the order they are made), each step taking twice the lighter head, the leaf when both weigh the same; the leaves'
+ *            depths counted per length, depths past max_len counted as max_len; while the Kraft sum (in units of 2^-max_len)
+ *            exceeds 1: one code less of length max_len, and the longest length below max_len that has a code gives one up for two
+ *            of the next length; then lengths are dealt out in increasing order from the most frequent end of the sorted list.
+ * pf_deflate_tile_bgr: host, one tile.  out = NULL: *len = the bound above.  Else *len = the stream's length; 0 if cap is smaller.
+ * pf_deflate_tiles_device: n tiles anywhere in one device allocation (tile i begins byte_offsets[i] >= 0 bytes behind dev_base, rows
+ * of `step` bytes, all 256 x 256 pixels inside the allocation), encoded on the GPU (csrc/deflate_encode.hip), byte-equal to the
+ * host encoder; offsets[0..n] = where stream i begins among the streams laid back to back; out (may be NULL: offsets only) takes
+ * them when cap >= offsets[n].  Only streams and offsets cross to the host.                                                    */
+int     pf_deflate_tile_bgr(const uint8_t* tile, size_t step, uint8_t* out, size_t cap, size_t* len);
+int     pf_deflate_tiles_device(const void* dev_base, int n, const long long* byte_offsets, size_t step, uint8_t* out, size_t cap,
+                                size_t* offsets, void* hip_stream);
+int     pf_deflate_code_lengths(const uint32_t* freq, int n, int max_len, uint8_t* out);
+/* The lossless pyramid TIFF: the file of pf_tiff_write_bgr (mask == NULL) or pf_tiff_write_bgr_masked with every colour tile a
+ * stream of the codec above instead of a JPEG one.  The colour IFDs carry Compression 8 (Adobe Deflate), PhotometricInterpretation
+ * 2 (RGB), Predictor (317, between 284 and 322) = 2 and no YCbCrSubSampling; the shared empty stream is the codec applied to a tile
+ * of the background colour.  Images, overviews, tile order, empty tiles, masks, geo tags, even offsets and the classic / BigTIFF
+ * choice are those of the JPEG file (the same tiff::layout_as).  Reading it back gives image k exactly.  Host code, no device. */
+int     pf_tiff_write_bgr_lossless(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step,
+                                   const uint8_t* mask, size_t mask_step, int bg,
+                                   const double model_transform[16], int force_bigtiff);
+/* The same file, byte for byte, from an image (and a mask, or NULL) in device memory: pf_tiff_write_device[_masked] with the tiles
+ * through csrc/deflate_encode.hip. */
+int     pf_tiff_write_device_lossless(const char* filename, const void* dev_bgr, int rows, int cols, size_t step,
+                                      const void* dev_mask, size_t mask_step, int bg,
+                                      const double model_transform[16], int force_bigtiff, void* hip_stream);
+/* A map's mosaic as that file, under any name: pf_tiff_write_bgr_lossless of the pixels (and, masked != 0, the mask)
+ * pf_save_to_memory[_mask] returns, Result.BackGroundColor and pf_save_tiff's T.  Multi-band maps encode on the GPU from the mosaic
+ * where the collapse left it, under the one hold of the map; single-band maps take the host writer.  pf_save("x.tif") and
+ * pf_save_tiff keep writing JPEG tiles. */
+int     pf_save_tiff_lossless(pf_map* m, const char* filename, int masked, int force_bigtiff);
 /* cv::imencode(".jpg") / the JPEG leg of cv::imwrite of OpenCV 2.4.9: baseline JPEG, byte for byte what libjpeg writes after
  * jpeg_set_defaults, JCS_RGB input and jpeg_set_quality(quality, TRUE) -- JFIF 1.01, 4:2:0, the Annex K tables, one interleaved
  * scan, integer colour conversion and ISLOW DCT.  bgr: rows x cols 8-bit BGR, `step` bytes per row (0 = packed).  quality is
@@ -253,6 +307,10 @@ int     pf_jpeg_decode_device(const uint8_t* data, size_t len, void* dev_bgr, in
  * launches the most recent GPU pass took } of the map's decoder (m = NULL: of pf_jpeg_decode_device's).  Sequential one-scan streams,
  * with or without restart intervals, take the GPU pass (csrc/jpeg_huff_par.hpp); PF_JPEG_HOST_HUFFMAN=1 keeps every stream on the host.  */
 void    pf_debug_jpeg_huffman(pf_map* m, long long out[3]);
+/* Diagnostics of the last pyramid TIFF made on the GPU (JPEG or lossless tiles) by the map m, or, m == NULL, by the process-wide
+ * writer behind pf_tiff_write_device* on the current device: out = { tiles of all images, the tiles among them found empty on the
+ * GPU (they share one stream and are not encoded), bytes of device memory held for levels and flags }; zeros before the first. */
+void    pf_debug_tiff_counts(pf_map* m, long long out[3]);
 /* Map2D::feed(cv::imread(imgfile), pose) in one call (backup/map2dfusion.cpp:129-135 + Map2DFusion.cpp:313-327): markers and
  * Huffman on the calling thread, then the frame is finished on the GPU straight into the slot in HBM a host frame would have
  * been uploaded to, and queued (thread=1) or rendered (thread=0) from there.  Returns what pf_feed returns.             */
@@ -632,6 +690,8 @@ int      pf_dist_blend_changed(pf_dist* d, int* xy, uint8_t* bgr, int cap);
 /* save() across ranks: every tile travels once to rank 0, which runs the whole-mosaic collapse and (pf_dist_save) writes
  * the file.  On the other ranks the calls return 1 with rows = cols = 0.                                            */
 int      pf_dist_save(pf_dist* d, const char* filename);
+/* ... as the lossless pyramid TIFF: rank 0 writes pf_save_tiff_lossless's file of the gathered mosaic */
+int      pf_dist_save_tiff_lossless(pf_dist* d, const char* filename, int masked, int force_bigtiff);
 int      pf_dist_save_to_memory(pf_dist* d, uint8_t* bgr, int* rows, int* cols, int* tile_x0, int* tile_y0);
 /* what the last pf_dist_* call moved */
 typedef struct pf_dist_stats {

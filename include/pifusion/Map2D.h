@@ -174,6 +174,8 @@ public:
     void fuseGoogle(bool on, double lng = 0, double lat = 0, double alt = 0) { fuse2google_ = on; gps_origin_[0] = lng; gps_origin_[1] = lat; gps_origin_[2] = alt; }
     // .png, .jpg / .jpeg, .tif / .tiff (tiled pyramid TIFF with JPEG tiles, overviews and geo tags), else PPM: see pf_save
     bool save(const std::string& filename) { return pf_save(h_, filename.c_str()) != 0; }
+    // the mosaic as a tiled pyramid TIFF with lossless (Deflate, Predictor 2) tiles, under any name (pf_save_tiff_lossless)
+    bool saveLossless(const std::string& filename, bool masked = false, bool force_bigtiff = false) { return pf_save_tiff_lossless(h_, filename.c_str(), masked, force_bigtiff) != 0; }
     bool saveTiff(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
     // the pyramid TIFF with a transparency mask behind every image: covered where the level-0 weight is not 0 (pf_save_tiff_masked)
     bool saveMasked(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff_masked(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }

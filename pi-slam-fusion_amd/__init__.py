@@ -144,6 +144,14 @@ def lib():
         L.pf_tiff_write_device_masked.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, dp, C.c_int, vp]
         L.pf_save_tiff_masked.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
         L.pf_save_to_memory_mask.argtypes = [vp, vp, vp, ip, ip, ip, ip]
+    if hasattr(L, "pf_deflate_tile_bgr") or not os.environ.get("PF_LIB"):
+        L.pf_deflate_tile_bgr.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.pf_deflate_tiles_device.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+        L.pf_deflate_code_lengths.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.pf_tiff_write_bgr_lossless.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, dp, C.c_int]
+        L.pf_tiff_write_device_lossless.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, dp, C.c_int, vp]
+        L.pf_save_tiff_lossless.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
+        L.pf_debug_tiff_counts.argtypes = [vp, C.POINTER(C.c_longlong)]; L.pf_debug_tiff_counts.restype = None
     if hasattr(L, "pf_webtiles") or not os.environ.get("PF_LIB"):
         L.pf_webtiles_georef.argtypes = [vp, dp, dp, ip, ip]
         L.pf_webtiles_georef_compose.argtypes = [dp, dp, dp, dp]
@@ -229,6 +237,8 @@ def lib():
     L.pf_dist_feed.argtypes = [vp, C.POINTER(Image), dp, C.c_int]
     L.pf_dist_feed_jpeg.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, dp, C.c_int]
     L.pf_dist_save.argtypes = [vp, C.c_char_p]
+    if hasattr(L, "pf_dist_save_tiff_lossless") or not os.environ.get("PF_LIB"):
+        L.pf_dist_save_tiff_lossless.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
     L.pf_dist_save_to_memory.argtypes = [vp, vp, ip, ip, ip, ip]
     L.pf_dist_last_stats.argtypes = [vp, C.POINTER(DistStats)]
     L.pf_dist_info.argtypes = [vp, ip, ip, C.POINTER(C.c_char_p)]
@@ -449,6 +459,81 @@ def tiff_write_device_masked(filename, dev_ptr, rows, cols, dev_mask, quality=95
     """The same file, byte for byte, from pixels and a byte-per-pixel mask at device addresses (csrc/coverage.hip beside overview.hip)."""
     keep, xf = _transform16(model_transform)
     return bool(lib().pf_tiff_write_device_masked(filename.encode(), dev_ptr, rows, cols, step, dev_mask, mask_step, quality, bg, xf, int(force_bigtiff), stream))
+
+
+DEFLATE_TILE_BOUND = 196608 + 5 * 16 + 6          # no tile stream is longer (include/pifusion.h)
+
+
+def deflate_tile(tile):
+    """256x256x3 BGR uint8 (rows may be padded) -> the tile's zlib stream of pf_deflate_tile_bgr (include/pifusion.h): Predictor 2,
+    run-length tokens at distance 1, 16 blocks, dynamic Huffman or stored.  Host code."""
+    a = np.asarray(tile)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(tile, dtype=np.uint8)
+    if a.shape != (256, 256, 3):
+        raise ValueError("deflate_tile: 256x256x3 expected")
+    out = np.empty(DEFLATE_TILE_BOUND, np.uint8)
+    n = C.c_size_t(0)
+    if not lib().pf_deflate_tile_bgr(a.ctypes.data, a.strides[0], out.ctypes.data, out.size, C.byref(n)):
+        raise RuntimeError("pf_deflate_tile_bgr failed: %s" % lib().pf_last_error().decode())
+    return out[:n.value].tobytes()
+
+
+def deflate_code_lengths(freq, max_len):
+    """the codec's length builder (pf_deflate_code_lengths): counts -> code lengths, none above max_len"""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    out = np.zeros(f.size, np.uint8)
+    if not lib().pf_deflate_code_lengths(f.ctypes.data, f.size, max_len, out.ctypes.data):
+        raise ValueError("pf_deflate_code_lengths failed: %s" % lib().pf_last_error().decode())
+    return out
+
+
+def deflate_tiles_device(dev_ptr, byte_offsets, step, stream=None):
+    """The streams of the tiles that begin byte_offsets[i] bytes behind the device address `dev_ptr` (rows of `step` bytes), encoded on
+    the GPU (csrc/deflate_encode.hip): a list of bytes objects, each equal to deflate_tile of the same pixels."""
+    w = np.ascontiguousarray(byte_offsets, dtype=np.int64)
+    n = int(w.size)
+    off = np.zeros(n + 1, np.uint64)
+    out = np.empty(n * DEFLATE_TILE_BOUND, np.uint8)
+    if not lib().pf_deflate_tiles_device(dev_ptr, n, w.ctypes.data, step, out.ctypes.data, out.size, off.ctypes.data, stream):
+        raise RuntimeError("pf_deflate_tiles_device failed: %s" % lib().pf_last_error().decode())
+    return [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+
+
+def tiff_write_lossless(filename, bgr, mask=None, bg=0, model_transform=None, force_bigtiff=False):
+    """tiff_write / tiff_write_masked with lossless tiles (pf_tiff_write_bgr_lossless): Compression 8, Predictor 2, every tile the
+    stream of deflate_tile.  mask None: the unmasked file.  Host code."""
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(bgr, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("tiff_write_lossless: HxWx3 expected")
+    mp, ms = None, 0
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.dtype == np.bool_:
+            m = m.astype(np.uint8)
+        if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+            m = np.ascontiguousarray(m, dtype=np.uint8)
+        if m.shape != a.shape[:2]:
+            raise ValueError("tiff_write_lossless: HxWx3 and HxW expected")
+        mp, ms = m.ctypes.data, m.strides[0]
+    keep, xf = _transform16(model_transform)
+    return bool(lib().pf_tiff_write_bgr_lossless(filename.encode(), a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], mp, ms, bg, xf, int(force_bigtiff)))
+
+
+def tiff_write_device_lossless(filename, dev_ptr, rows, cols, dev_mask=None, bg=0, model_transform=None, force_bigtiff=False, step=0, mask_step=0, stream=None):
+    """The same file, byte for byte, from pixels (and a byte-per-pixel mask, or None) at device addresses (csrc/overview.hip + deflate_encode.hip)."""
+    keep, xf = _transform16(model_transform)
+    return bool(lib().pf_tiff_write_device_lossless(filename.encode(), dev_ptr, rows, cols, step, dev_mask, mask_step, bg, xf, int(force_bigtiff), stream))
+
+
+def tiff_counts(map2d=None):
+    """(tiles of all images, the empty ones among them, bytes of device memory held for levels and flags) of the last pyramid TIFF the
+    map -- or, map2d None, the process-wide writer behind tiff_write_device* on the current device -- made on the GPU (pf_debug_tiff_counts)"""
+    out = (C.c_longlong * 3)()
+    lib().pf_debug_tiff_counts(map2d._h if map2d is not None else None, out)
+    return tuple(int(v) for v in out)
 
 
 def jpeg_huffman_counts(map2d=None):
@@ -850,6 +935,10 @@ class Map2D:
     def save_tiff_masked(self, filename, quality=95, force_bigtiff=False):
         """save_tiff with a transparency mask behind every image: covered where the level-0 weight is not 0 (pf_save_tiff_masked)"""
         return bool(lib().pf_save_tiff_masked(self._h, filename.encode(), quality, int(force_bigtiff)))
+
+    def save_tiff_lossless(self, filename, masked=False, force_bigtiff=False):
+        """the mosaic as a pyramid TIFF with lossless (Deflate) tiles, with or without the transparency masks (pf_save_tiff_lossless)"""
+        return bool(lib().pf_save_tiff_lossless(self._h, filename.encode(), int(masked), int(force_bigtiff)))
 
     def save_to_memory_mask(self):
         """(mosaic BGR8, coverage HxW uint8: 255 where the level-0 weight is not 0, (tile x0, tile y0)) of one moment"""

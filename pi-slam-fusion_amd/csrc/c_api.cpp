@@ -113,6 +113,7 @@ unsigned pf_queue_size(pf_map* m) { return m ? m->impl.queue_size() : 0; }
 int pf_sync(pf_map* m) { return m && m->impl.sync(); }
 int pf_save(pf_map* m, const char* filename) { return m && filename && m->impl.save(filename); }
 int pf_save_tiff(pf_map* m, const char* filename, int quality, int force_bigtiff) { return m && filename && m->impl.save_tiff(filename, quality, force_bigtiff != 0); }
+int pf_save_tiff_lossless(pf_map* m, const char* filename, int masked, int force_bigtiff) { return m && filename && m->impl.save_tiff_lossless(filename, masked != 0, force_bigtiff != 0); }
 int pf_save_tiff_masked(pf_map* m, const char* filename, int quality, int force_bigtiff) { return m && filename && m->impl.save_tiff_masked(filename, quality, force_bigtiff != 0); }
 // pf_write_image / pf_image_info / pf_read_image: image_io.cpp (host code without a HIP dependency: also built by the sanitizer targets)
 int pf_jpeg_info(const uint8_t* data, size_t len, int* rows, int* cols, int* components) { return pf::jpeg_info(data, len, rows, cols, components); }
@@ -211,6 +212,71 @@ int pf_tiff_write_device_masked(const char* filename, const void* dev_bgr, int r
     const int ok = shared_tiff_device(at.device)->write(filename, dev_bgr, rows, cols, step, quality, bg, model_transform, force_bigtiff != 0, *shared_jpeg_encoder(at.device), hip_stream, &mk);
     if (at.device != prev) (void)hipSetDevice(prev);
     return ok;
+}
+// pf_deflate_tiles_device's and pf_tiff_write_device_lossless's encoder: one per device, as the JPEG one
+static pf::DeflateEncoder* shared_deflate_encoder(int device)
+{
+    static pf::DeflateEncoder* e[64] = {};
+    if (device < 0 || device >= 64) device = 0;
+    if (!e[device]) e[device] = new pf::DeflateEncoder();
+    return e[device];
+}
+int pf_deflate_tiles_device(const void* dev_base, int n, const long long* byte_offsets, size_t step, uint8_t* out, size_t cap, size_t* offsets, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_jpeg_mu);
+    if (!dev_base || n <= 0 || !byte_offsets || !offsets) { pf::set_error("pf_deflate_tiles_device: no image, no tiles or no room for the offsets"); return 0; }
+    if (step == 0) step = (size_t)pf::dfl::kRowBytes;
+    if (step < (size_t)pf::dfl::kRowBytes) { pf::set_error("pf_deflate_tiles_device: step is smaller than a row"); return 0; }
+    for (int i = 0; i < n; i++) if (byte_offsets[i] < 0) { pf::set_error("pf_deflate_tiles_device: a tile begins in front of the allocation"); return 0; }
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dev_base) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_deflate_tiles_device: the image is not in device memory"); return 0; }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_deflate_tiles_device: hipSetDevice failed"); return 0; }
+    pf::DeflateEncoder* e = shared_deflate_encoder(at.device);
+    int ok = e->encode_windows(dev_base, n, byte_offsets, step, offsets, hip_stream);
+    if (ok && out) {
+        if (offsets[n] > cap) { pf::set_error("pf_deflate_tiles_device: the streams have " + std::to_string(offsets[n]) + " bytes, the buffer " + std::to_string(cap)); ok = 0; }
+        else ok = e->fetch(out, hip_stream);
+    }
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
+int pf_tiff_write_device_lossless(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, const void* dev_mask, size_t mask_step, int bg,
+                                  const double model_transform[16], int force_bigtiff, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_jpeg_mu);
+    if (!filename || !dev_bgr || rows <= 0 || cols <= 0) { pf::set_error("pf_tiff_write_device_lossless: no name, no image or a size that is not positive"); return 0; }
+    if (step == 0) step = (size_t)cols * 3;
+    if (mask_step == 0) mask_step = (size_t)cols;
+    if (step < (size_t)cols * 3 || (dev_mask && mask_step < (size_t)cols)) { pf::set_error("pf_tiff_write_device_lossless: step is smaller than a row"); return 0; }
+    hipPointerAttribute_t at{}, am{};
+    if (hipPointerGetAttributes(&at, dev_bgr) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_tiff_write_device_lossless: the image is not in device memory"); return 0; }
+    if (dev_mask && (hipPointerGetAttributes(&am, dev_mask) != hipSuccess || am.type != hipMemoryTypeDevice || am.device != at.device)) {
+        (void)hipGetLastError(); pf::set_error("pf_tiff_write_device_lossless: the mask is not in device memory beside the image"); return 0;
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_tiff_write_device_lossless: hipSetDevice failed"); return 0; }
+    pf::TiffDevice::Mask mk;
+    mk.dev_bytes = dev_mask; mk.step = mask_step;
+    const int ok = shared_tiff_device(at.device)->write(filename, dev_bgr, rows, cols, step, 0, bg, model_transform, force_bigtiff != 0, *shared_jpeg_encoder(at.device), hip_stream,
+                                                        dev_mask ? &mk : nullptr, shared_deflate_encoder(at.device));
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
+void pf_debug_tiff_counts(pf_map* m, long long out[3])
+{
+    if (!out) return;
+    size_t t = 0, e = 0, b = 0;
+    if (m) m->impl.tiff_counts(&t, &e, &b);
+    else {
+        std::lock_guard<std::mutex> l(g_jpeg_mu);
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+        shared_tiff_device(dev)->last_counts(&t, &e, &b);
+    }
+    out[0] = (long long)t; out[1] = (long long)e; out[2] = (long long)b;
 }
 void pf_debug_jpeg_huffman(pf_map* m, long long out[3])
 {
@@ -756,6 +822,7 @@ int pf_dist_feed_jpeg(pf_dist* d, const uint8_t* data, size_t len, int rows, int
     };
     return d->impl.feed(&img, pose, root, &fill);
 }
+int pf_dist_save_tiff_lossless(pf_dist* d, const char* filename, int masked, int force_bigtiff) { return d && filename && d->impl.save_tiff_lossless(filename, masked != 0, force_bigtiff != 0); }
 int pf_dist_save(pf_dist* d, const char* filename) { return d && filename && d->impl.save(filename); }
 int pf_dist_save_to_memory(pf_dist* d, uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0)
 { return d && rows && cols && tx0 && ty0 && d->impl.save_to_memory(bgr, rows, cols, tx0, ty0); }

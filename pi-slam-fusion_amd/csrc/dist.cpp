@@ -488,15 +488,20 @@ int DistMap::feed(const pf_image* img, const double pose7[7], int root, const Fu
 }
 
 // every rank makes the call (the gather is collective); rank 0 writes the file, by the same route a map of its own would take
-bool DistMap::save(const char* filename)
+bool DistMap::save(const char* filename) { return save_routed(filename, save_route(filename, m_->single_band()), 95, false, false); }
+// ... the lossless pyramid TIFF (pf_dist_save_tiff_lossless): rank 0 encodes the gathered mosaic as a map of its own would
+bool DistMap::save_tiff_lossless(const char* filename, bool masked, bool force_bigtiff)
+{ return save_routed(filename, tiff_lossless_route(m_->single_band()), 0, force_bigtiff, masked); }
+
+bool DistMap::save_routed(const char* filename, SaveRoute route, int quality, bool force_bigtiff, bool masked)
 {
     if (!m_->use_device()) return false;
-    if (t_->nranks == 1) return m_->save(filename);
+    if (t_->nranks == 1) return m_->save_file(filename, route, quality, force_bigtiff, nullptr, masked);
     SaveGather g;
     if (!save_lists(g) || !g.count || !save_tiles(g)) return false;
     if (t_->rank != 0) return true;
     const auto t_x = std::chrono::steady_clock::now();
-    const bool ok = m_->save_file(filename, save_route(filename, m_->single_band()), 95, false, &g.foreign);
+    const bool ok = m_->save_file(filename, route, quality, force_bigtiff, &g.foreign, masked);
     stats_.compute_ms = ms_since(t_x);
     return ok;
 }

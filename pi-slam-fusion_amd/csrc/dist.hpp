@@ -30,6 +30,7 @@ public:
     int  blend_changed(int* xy, uint8_t* bgr, int cap);        // tiles blended on this rank, -1 on failure
     bool save_to_memory(uint8_t* bgr, int* rows, int* cols, int* tx0, int* ty0);
     bool save(const char* filename);
+    bool save_tiff_lossless(const char* filename, bool masked, bool force_bigtiff);
     // 1 rendered / accepted, 0 rejected, -1 failure.  `produce` (root only, img->data == nullptr): the root's pixels are written into its
     // staged slot by the caller's own work on the map's stream (pf_dist_feed_jpeg: the decoder) instead of being uploaded
     int  feed(const pf_image* img, const double pose7[7], int root, const FusionMap::FrameProducer* produce = nullptr);
@@ -46,6 +47,7 @@ private:
         size_t count = 0; int rows = 0, cols = 0, tx0 = 0, ty0 = 0;
         std::vector<FusionMap::ForeignTile> foreign;
     };
+    bool save_routed(const char* filename, SaveRoute route, int quality, bool force_bigtiff, bool masked);
     bool save_lists(SaveGather& g);
     bool save_tiles(SaveGather& g);
     bool agree(bool ok_here);

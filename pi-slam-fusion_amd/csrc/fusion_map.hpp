@@ -78,6 +78,10 @@ public:
     bool save_tiff(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff); }
     // save_tiff() with a transparency mask behind every image (pf_save_tiff_masked): covered = the level-0 weight is not 0
     bool save_tiff_masked(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff, nullptr, true); }
+    // the lossless file (pf_save_tiff_lossless): a TIFF under any name with Deflate tiles, masked or not
+    bool save_tiff_lossless(const char* filename, bool masked, bool force_bigtiff) { return save_file(filename, tiff_lossless_route(single_band_), 0, force_bigtiff, nullptr, masked); }
+    // pf_debug_tiff_counts: tiles, empty tiles and device bytes of the last TIFF this map made on the GPU
+    void tiff_counts(size_t* tiles, size_t* empty, size_t* device_bytes) { std::lock_guard<std::mutex> l(mu_); tiff_dev_.last_counts(tiles, empty, device_bytes); }
     // pf_webtiles: what the tiles are made for and where they go
     struct WebTilesJob { const double* gps_origin; int zmin, zmax, quality; bool want_pixels; pf_webtile_sink sink; void* user;
                          double* report; };          // report (may be null): px2ll[6], rows, cols of the mosaic the tiles are made from
@@ -427,6 +431,7 @@ private:
     DevBuf blend_lv_[kMaxLevels], blend_src_, blend_out_raw_, blend_out_bgr_, mosaic_table_, strip_desc_;
     DevBuf cover_plane_, cover_bytes_;          // pf_save_to_memory_mask: the mosaic's coverage as a bit plane (coverage.hip), and as bytes
     TiffDevice  tiff_dev_;      // save("x.tif"): level buffers and flags of its own, tiles through jpeg_enc_
+    DeflateEncoder deflate_enc_;   // save_tiff_lossless(): the tiles of tiff_dev_'s levels on stream_, buffers of its own
     JpegEncoder jpeg_enc_;      // save("x.jpg"), pf_blend_tiles_jpeg: reads blend_out_bgr_ on stream_, buffers of its own
     OutRing     out_ring_;      // results on their way to the host
     bool export_webtiles(const SaveTarget& t, const WebTilesJob& job);                        // blend_out_bgr_ + cover_bytes_ of extent t -> the job's map tiles

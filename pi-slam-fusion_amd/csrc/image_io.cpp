@@ -162,6 +162,17 @@ bool write_tiff_masked_file(const char* who, const char* filename, const uint8_t
     catch (const std::bad_alloc&) { std::remove(filename); set_error(std::string(who) + ": out of memory"); return false; }
 }
 
+bool write_tiff_lossless_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                              int bg, const double* model_transform, bool force_bigtiff)
+{
+    if (!filename || !bgr || rows <= 0 || cols <= 0) { set_error(std::string(who) + ": no name, no image or a size that is not positive"); return false; }
+    if (step == 0) step = (size_t)cols * 3;
+    if (mask_step == 0) mask_step = (size_t)cols;
+    if (step < (size_t)cols * 3 || (mask && mask_step < (size_t)cols)) { set_error(std::string(who) + ": step is smaller than a row"); return false; }
+    try { return tiff::write_pyramid(filename, bgr, rows, cols, step, mask, mask_step, 0, bg, model_transform, force_bigtiff, tiff::kDeflate); }
+    catch (const std::bad_alloc&) { std::remove(filename); set_error(std::string(who) + ": out of memory"); return false; }
+}
+
 bool jpeg_size_ok(const char* who, int rows, int cols)
 {
     if (rows <= jenc::kMaxDim && cols <= jenc::kMaxDim) return true;
@@ -232,6 +243,29 @@ int pf_tiff_write_bgr(const char* filename, const uint8_t* bgr, int rows, int co
 int pf_tiff_write_bgr_masked(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
                              int quality, int bg, const double model_transform[16], int force_bigtiff)
 { return pf::write_tiff_masked_file("pf_tiff_write_bgr_masked", filename, bgr, rows, cols, step, mask, mask_step, quality, bg, model_transform, force_bigtiff != 0); }
+int pf_tiff_write_bgr_lossless(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step, int bg,
+                               const double model_transform[16], int force_bigtiff)
+{ return pf::write_tiff_lossless_file("pf_tiff_write_bgr_lossless", filename, bgr, rows, cols, step, mask, mask_step, bg, model_transform, force_bigtiff != 0); }
+int pf_deflate_tile_bgr(const uint8_t* tile, size_t step, uint8_t* out, size_t cap, size_t* len)
+{
+    if (!tile || !len) { pf::set_error("pf_deflate_tile_bgr: no tile or no length"); return 0; }
+    if (step == 0) step = (size_t)pf::dfl::kRowBytes;
+    if (step < (size_t)pf::dfl::kRowBytes) { pf::set_error("pf_deflate_tile_bgr: step is smaller than a row"); return 0; }
+    if (!out) { *len = pf::dfl::kStreamBound; return 1; }
+    std::vector<uint8_t> stream;
+    try { pf::dfl::encode_tile(tile, step, stream); } catch (const std::bad_alloc&) { pf::set_error("pf_deflate_tile_bgr: out of memory"); return 0; }
+    *len = stream.size();
+    if (stream.size() > cap) { pf::set_error("pf_deflate_tile_bgr: the stream has " + std::to_string(stream.size()) + " bytes, the buffer " + std::to_string(cap)); return 0; }
+    std::memcpy(out, stream.data(), stream.size());
+    return 1;
+}
+int pf_deflate_code_lengths(const uint32_t* freq, int n, int max_len, uint8_t* out)
+{
+    if (!freq || !out) { pf::set_error("pf_deflate_code_lengths: no counts or no room for the lengths"); return 0; }
+    pf::dfl::Work w;
+    if (!pf::dfl::code_lengths(freq, n, max_len, out, w)) { pf::set_error("pf_deflate_code_lengths: 2 <= n <= 288, 1 <= max_len <= 15 and 2^max_len >= n are required"); return 0; }
+    return 1;
+}
 int pf_image_info(const char* filename, int* rows, int* cols)
 {
     if (!filename || !rows || !cols) return 0;

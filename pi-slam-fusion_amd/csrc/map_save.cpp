@@ -124,11 +124,11 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
         return out_ring_.download(stream_, pieces);
     }
     // the mosaic stays where the collapse left it
-    if (t.route == SaveRoute::DeviceTiff) {        // overviews, empty test and tile streams are made from it there; the masks from the table
+    if (t.route == SaveRoute::DeviceTiff || t.route == SaveRoute::DeviceTiffLossless) {        // overviews, empty test and tile streams are made from it there; the masks from the table
         TiffDevice::Mask mk;
         mk.dev_table = (const uint64_t*)mosaic_table_.p; mk.wx = wx; mk.wy = wy; mk.w_off = lay_.w_off[0];
         return tiff_dev_.write(t.name, blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, t.quality, opt_.bg_color, t.transform, t.force_bigtiff, jpeg_enc_, stream_,
-                               t.masked ? &mk : nullptr);
+                               t.masked ? &mk : nullptr, t.route == SaveRoute::DeviceTiffLossless ? &deflate_enc_ : nullptr);
     }
     size_t off[2];                                 // cv::imwrite's JPEG defaults: quality 95, 4:2:0
     if (!jpeg_enc_.encode(blend_out_bgr_.p, 1, nullptr, 0, t.rows, t.cols, (size_t)t.cols * 3, t.quality, off, stream_)) return false;
@@ -218,6 +218,8 @@ bool FusionMap::save_file(const char* filename, SaveRoute route, int quality, bo
         if (masked ? !write_tiff_masked_file("save", filename, img.data(), t.rows, t.cols, 0, cover.data(), 0, quality, opt_.bg_color, t.transform, force_bigtiff)
                    : !write_tiff_file("save", filename, img.data(), t.rows, t.cols, 0, quality, opt_.bg_color, t.transform, force_bigtiff)) return false;
     }
+    if (route == SaveRoute::HostTiffLossless &&
+        !write_tiff_lossless_file("save", filename, img.data(), t.rows, t.cols, 0, masked ? cover.data() : nullptr, 0, opt_.bg_color, t.transform, force_bigtiff)) return false;
     if (route == SaveRoute::HostImage && !write_image_file(filename, img.data(), t.rows, t.cols)) return false;
     std::printf("Resolution:[%d %d]\n", t.cols, t.rows);
     return true;

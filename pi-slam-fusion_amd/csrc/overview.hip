@@ -172,7 +172,8 @@ inline size_t round_tile(int v) { return (size_t)((v + kTile - 1) / kTile) * kTi
         if (e_ != hipSuccess) { set_error(std::string("tiff: " #expr ": ") + hipGetErrorString(e_)); return false; }  \
     } while (0)
 
-// tiles per encoder pass: bounds the encoder's scratch (about 230 KB of coefficients and offsets per tile) whatever the mosaic's size
+// tiles per encoder pass: bounds the encoder's scratch (JPEG: about 230 KB of coefficients and offsets per tile; Deflate: the
+// worst-case stream, 197 KB, and 13 KB of block plans) whatever the mosaic's size
 constexpr size_t kBatchTiles = 512;
 
 struct TiffDevice::Impl {
@@ -221,8 +222,9 @@ void TiffDevice::last_mask_counts(size_t* zero, size_t* one, size_t* own_bytes) 
 }
 
 bool TiffDevice::write(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff,
-                       JpegEncoder& enc, void* stream, const Mask* mask)
+                       JpegEncoder& enc, void* stream, const Mask* mask, DeflateEncoder* lossless)
 {
+    const Codec codec = lossless ? kDeflate : kJpeg;
     hipStream_t s = (hipStream_t)stream;
     if (!filename || !dev_bgr || rows < 1 || cols < 1) { set_error("tiff: no name, no image or a size that is not positive"); return false; }
     if (step == 0) step = (size_t)cols * 3;
@@ -352,24 +354,25 @@ bool TiffDevice::write(const char* filename, const void* dev_bgr, int rows, int 
             }
             if (win.empty()) continue;
             const int n = (int)win.size();
-            if (!enc.encode_windows(base[k], n, win.data(), kTile, kTile, lstep[k], quality, off.data(), stream)) return false;
+            if (lossless ? !lossless->encode_windows(base[k], n, win.data(), lstep[k], off.data(), stream)
+                         : !enc.encode_windows(base[k], n, win.data(), kTile, kTile, lstep[k], quality, off.data(), stream)) return false;
             done += (size_t)n;
             // room for the batch; the first time round the whole file's streams are guessed from the first batch
             if (!d.grow_land(used + off[n], used, (size_t)((double)(used + off[n]) / (double)done * (double)n_full * 1.15))) return false;
-            if (!enc.fetch(d.land + used, stream)) return false;
+            if (lossless ? !lossless->fetch(d.land + used, stream) : !enc.fetch(d.land + used, stream)) return false;
             for (int j = 0; j < n; j++) { where[who[j]] = used + off[j]; len[who[j]] = (uint32_t)(off[j + 1] - off[j]); }
             used += off[n];
         }
     }
     std::vector<uint8_t> empty;
-    empty_stream(quality, bg, empty);
+    empty_stream(quality, bg, empty, codec);
     Layout lo;
     if (!mask) {
-        layout(lv, len, (uint32_t)empty.size(), model_transform, force_bigtiff, lo);
+        layout_masked(lv, len, (uint32_t)empty.size(), nullptr, model_transform, force_bigtiff, lo, codec);
         return write_file(filename, lo, len, empty, [&](size_t i) { return (const uint8_t*)d.land + where[i]; });
     }
     TIFF_OK(hipStreamSynchronize(s));          // the gathered mask tiles have landed
-    layout_masked(lv, len, (uint32_t)empty.size(), &mkind, model_transform, force_bigtiff, lo);
+    layout_masked(lv, len, (uint32_t)empty.size(), &mkind, model_transform, force_bigtiff, lo, codec);
     const std::function<const uint8_t*(size_t)> mtile = [&](size_t i) { return (const uint8_t*)d.mland + mwhere[i]; };
     return write_file(filename, lo, len, empty, [&](size_t i) { return (const uint8_t*)d.land + where[i]; }, &mkind, &mtile);
 }

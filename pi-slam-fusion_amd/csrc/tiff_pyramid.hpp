@@ -10,8 +10,12 @@
 // The masked file (pf_tiff_write_bgr_masked) is the same file with a transparency mask behind every image: 1 bit per pixel,
 // uncompressed tiles of 256 rows x 32 bytes, image k + 1's mask the OR of the 2 x 2 blocks of image k's, all-zero and all-one
 // tiles stored once.  The same layout function places it; with no mask it places today's bytes.
+//
+// The lossless file (pf_tiff_write_bgr_lossless) is either of the two with Codec kDeflate: every colour tile a zlib stream of
+// deflate_rle.hpp, the colour IFDs saying Compression 8, RGB, Predictor 2.  With kJpeg, the default, nothing changes.
 #pragma once
 #include "jpeg_encode.hpp"
+#include "deflate_rle.hpp"
 #include <cstdio>
 #include <functional>
 #include <string>
@@ -23,6 +27,9 @@ void set_error(const std::string& msg);          // jpeg_decode.cpp
 namespace tiff {
 
 constexpr int kTile = 256;
+// what a colour tile's stream is: a baseline JPEG (Compression 7, YCbCr 4:2:0), or a zlib stream of the tile's horizontally
+// differenced RGB bytes (deflate_rle.hpp: Compression 8, Predictor 2).  Everything else about the file is the same.
+enum Codec : int { kJpeg = 0, kDeflate = 1 };
 
 struct Level {
     int rows, cols;          // the image
@@ -79,7 +86,7 @@ inline Entry longs(uint16_t tag, std::initializer_list<unsigned> v) { Entry e{ t
 // len[i]: bytes of tile i's stream, 0 for an empty tile; empty_len: bytes of the shared stream.  model_transform may be null.
 // mkind (null: the unmasked file): the MaskKind of tile i's mask tile.  Then every image's IFD is followed by its mask's, the two
 // shared mask tiles lie behind the shared stream and the other mask tiles behind the last stream, image by image, row-major.
-inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const std::vector<uint8_t>* mkind, const double* model_transform, bool big, Layout& out)
+inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const std::vector<uint8_t>* mkind, const double* model_transform, bool big, Layout& out, Codec codec = kJpeg)
 {
     using namespace detail;
     out = Layout();
@@ -102,10 +109,11 @@ inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>&
         e.push_back(longs(256, { (unsigned)l.cols }));
         e.push_back(longs(257, { (unsigned)l.rows }));
         if (mask) e.push_back(shorts(258, { 1 })); else e.push_back(shorts(258, { 8, 8, 8 }));
-        e.push_back(shorts(259, { mask ? 1u : 7u }));
-        e.push_back(shorts(262, { mask ? 4u : 6u }));
+        e.push_back(shorts(259, { mask ? 1u : codec == kDeflate ? 8u : 7u }));
+        e.push_back(shorts(262, { mask ? 4u : codec == kDeflate ? 2u : 6u }));
         e.push_back(shorts(277, { mask ? 1u : 3u }));
         e.push_back(shorts(284, { 1 }));
+        if (!mask && codec == kDeflate) e.push_back(shorts(317, { 2 }));
         e.push_back(shorts(322, { (unsigned)kTile }));
         e.push_back(shorts(323, { (unsigned)kTile }));
         Entry to{ 324, (uint16_t)(big ? 16 : 4), n, std::vector<uint8_t>(n * osz, 0) };          // filled in below
@@ -113,7 +121,7 @@ inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>&
         Entry tb{ 325, 4, n, {} };
         for (size_t i = 0; i < n; i++) put(tb.value, mask ? (uint32_t)kMaskTileBytes : len[l.first + i] ? len[l.first + i] : empty_len, 4);
         e.push_back(tb);
-        if (!mask) e.push_back(shorts(530, { 2, 2 }));
+        if (!mask && codec == kJpeg) e.push_back(shorts(530, { 2, 2 }));
         if (k == 0 && !mask && model_transform) {
             Entry mt{ 34264, 12, 16, {} };
             for (int i = 0; i < 16; i++) { uint64_t bits; std::memcpy(&bits, &model_transform[i], 8); put(mt.value, bits, 8); }
@@ -176,19 +184,24 @@ inline bool layout_as(const std::vector<Level>& lv, const std::vector<uint32_t>&
     return true;
 }
 
-inline void layout_masked(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const std::vector<uint8_t>* mkind, const double* model_transform, bool force_bigtiff, Layout& out)
+inline void layout_masked(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const std::vector<uint8_t>* mkind, const double* model_transform, bool force_bigtiff, Layout& out, Codec codec = kJpeg)
 {
-    if (force_bigtiff || !layout_as(lv, len, empty_len, mkind, model_transform, false, out)) (void)layout_as(lv, len, empty_len, mkind, model_transform, true, out);
+    if (force_bigtiff || !layout_as(lv, len, empty_len, mkind, model_transform, false, out, codec)) (void)layout_as(lv, len, empty_len, mkind, model_transform, true, out, codec);
 }
 inline void layout(const std::vector<Level>& lv, const std::vector<uint32_t>& len, uint32_t empty_len, const double* model_transform, bool force_bigtiff, Layout& out)
 { layout_masked(lv, len, empty_len, nullptr, model_transform, force_bigtiff, out); }
 
 // the stream every empty tile points at: 256 x 256 pixels of the background colour
-inline void empty_stream(int quality, int bg, std::vector<uint8_t>& out)
+inline void encode_tile(Codec codec, const uint8_t* tile, int quality, std::vector<uint8_t>& out)
+{
+    if (codec == kDeflate) dfl::encode_tile(tile, (size_t)kTile * 3, out);
+    else jenc::encode_bgr(tile, kTile, kTile, (size_t)kTile * 3, quality, out);
+}
+inline void empty_stream(int quality, int bg, std::vector<uint8_t>& out, Codec codec = kJpeg)
 {
     std::vector<uint8_t> px((size_t)kTile * kTile * 3, background_byte(bg));
     out.clear();
-    jenc::encode_bgr(px.data(), kTile, kTile, (size_t)kTile * 3, quality, out);
+    encode_tile(codec, px.data(), quality, out);
 }
 
 // The file: the head, then the streams where the layout put them.  stream(i): the bytes of tile i (len[i] of them, len[i] > 0),
@@ -286,7 +299,7 @@ inline MaskKind cut_mask_tile(const uint8_t* cov, int rows, int cols, int ty, in
 
 // pf_tiff_write_bgr (mask == null) and pf_tiff_write_bgr_masked (mask: a byte per pixel, non-zero = covered, rows of mask_step bytes)
 inline bool write_pyramid(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
-                          int quality, int bg, const double* model_transform, bool force_bigtiff)
+                          int quality, int bg, const double* model_transform, bool force_bigtiff, Codec codec = kJpeg)
 {
     const std::vector<Level> lv = levels(rows, cols);
     const uint8_t bgv = background_byte(bg);
@@ -302,14 +315,14 @@ inline bool write_pyramid(const char* filename, const uint8_t* bgr, int rows, in
                 if (cut_tile(img, l.rows, l.cols, step, ty, tx, bgv, tile.data())) continue;
                 const size_t i = l.first + (size_t)ty * l.tx + tx;
                 at[i] = streams.size();
-                jenc::encode_bgr(tile.data(), kTile, kTile, (size_t)kTile * 3, quality, streams);
+                encode_tile(codec, tile.data(), quality, streams);
                 len[i] = (uint32_t)(streams.size() - at[i]);
             }
     }
-    empty_stream(quality, bg, empty);
+    empty_stream(quality, bg, empty, codec);
     Layout lo;
     if (!mask) {
-        layout(lv, len, (uint32_t)empty.size(), model_transform, force_bigtiff, lo);
+        layout_masked(lv, len, (uint32_t)empty.size(), nullptr, model_transform, force_bigtiff, lo, codec);
         return write_file(filename, lo, len, empty, [&](size_t i) { return streams.data() + at[i]; });
     }
     // the masks: the OR chain, every tile packed and classed; the tiles that are stored on their own are kept back to back
@@ -329,7 +342,7 @@ inline bool write_pyramid(const char* filename, const uint8_t* bgr, int rows, in
                 if (mkind[i] != kMaskOwn) mtiles.resize(mat[i]);
             }
     }
-    layout_masked(lv, len, (uint32_t)empty.size(), &mkind, model_transform, force_bigtiff, lo);
+    layout_masked(lv, len, (uint32_t)empty.size(), &mkind, model_transform, force_bigtiff, lo, codec);
     const std::function<const uint8_t*(size_t)> mtile = [&](size_t i) { return (const uint8_t*)mtiles.data() + mat[i]; };
     return write_file(filename, lo, len, empty, [&](size_t i) { return streams.data() + at[i]; }, &mkind, &mtile);
 }
@@ -357,8 +370,9 @@ public:
         const void* dev_bytes = nullptr; size_t step = 0;
         const uint64_t* dev_table = nullptr; int wx = 0, wy = 0; uint32_t w_off = 0;
     };
+    // `lossless` given: the colour tiles are its Deflate streams (Codec kDeflate; quality and `enc` are not used), else enc's JPEG ones
     bool write(const char* filename, const void* dev_bgr, int rows, int cols, size_t step, int quality, int bg, const double* model_transform, bool force_bigtiff,
-               JpegEncoder& enc, void* stream, const Mask* mask = nullptr);
+               JpegEncoder& enc, void* stream, const Mask* mask = nullptr, DeflateEncoder* lossless = nullptr);
     // diagnostics of the last write: tiles of all images, the empty ones among them, bytes of device memory held for levels and flags
     void last_counts(size_t* tiles, size_t* empty, size_t* device_bytes) const;
     // ... of the last masked write: mask tiles that are all zero, all one, and the bytes of the others (what crossed to the host)

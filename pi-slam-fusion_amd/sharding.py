@@ -138,6 +138,9 @@ class DistMap:
     def save(self, filename):
         return bool(_pkg().lib().pf_dist_save(self._h, filename.encode()))
 
+    def save_tiff_lossless(self, filename, masked=False, force_bigtiff=False):
+        return bool(_pkg().lib().pf_dist_save_tiff_lossless(self._h, filename.encode(), int(masked), int(force_bigtiff)))
+
     def set_verify(self, on=True):
         """hash every data exchange of the following calls on both ends (pf_dist_set_verify)"""
         _pkg().lib().pf_dist_set_verify(self._h, 1 if on else 0)
