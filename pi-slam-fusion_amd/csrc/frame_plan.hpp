@@ -55,20 +55,53 @@ struct TileCull {
     int nraise; int q[16]; float w[16]; // cells whose lower bound the keyframe raises: wlb[q] -> w, once the frame is in
 };
 
-// The canvas lattice (64 (k - dil), 64 (m - dil)), k = 0 .. ccols / 64 + 2 dil, mapped into the source frame: position, squared distance
-// from the image centre, inside-the-frame flag.  A cell's dilated rectangle has its corners on it.
+// The Lipschitz constant of a keyframe's map on its canvas: s >= sup ||J_H||_2 over the rectangle [x0, x1] x [y0, y1] of canvas pixels,
+// H(x) = (A x + b) / W(x), W(x) = g . x + h.  J = (A - H(x) g^T) / W(x), so ||J|| <= (||A||_2 + |H(x)| |g|) / |W(x)|; W is linear and keeps
+// its sign on the rectangle (cull_frame_ok asks for more), |H| is convex on the rectangle's image (a convex quadrilateral): both extrema
+// sit at corners.  The exact 2-norm of the 2 x 2 block (its largest singular value), not the Frobenius norm.
+inline double map_lipschitz(const double M[9], double x0, double x1, double y0, double y1)
+{
+    const double t = M[0] * M[0] + M[1] * M[1] + M[3] * M[3] + M[4] * M[4], det = M[0] * M[4] - M[1] * M[3];
+    const double nA = std::sqrt(0.5 * (t + std::sqrt(std::max(t * t - 4.0 * det * det, 0.0))));
+    const double xs[2] = { x0, x1 }, ys[2] = { y0, y1 };
+    double hmax = 0, wmin = 1e300;
+    for (int i = 0; i < 4; i++) {
+        const double x = xs[i & 1], y = ys[i >> 1], W = M[6] * x + M[7] * y + M[8];
+        hmax = std::max(hmax, std::hypot(M[0] * x + M[1] * y + M[2], M[3] * x + M[4] * y + M[5]) / std::fabs(W));
+        wmin = std::min(wmin, std::fabs(W));
+    }
+    const double s = (nA + hmax * std::hypot(M[6], M[7])) / wmin;
+    return std::isfinite(s) ? s : 1e30;
+}
+// The slack of the pyramid, source pixels: a weight of level i <= L is the level-0 weight image under the i-fold composition of pyrDown's
+// [1 4 6 4 1] / 16, centred on the pixel's own level-0 position with variance (4^i - 1) / 3 per axis (BORDER_REFLECT_101 only folds mass
+// towards positions inside the canvas), so E |x - 2^i p| <= sqrt(2 (4^L - 1) / 3) level-0 pixels, s times that in the source.
+inline double pyramid_slack(double s, int L)
+{
+    return L <= 0 ? 0.0 : s * std::sqrt(2.0 * (std::ldexp(1.0, 2 * L) - 1.0) / 3.0);
+}
+
+// The canvas lattice (64 (k - off), 64 (m - off)), k = 0 .. ccols / 64 + 2 off, mapped into the source frame: position, squared distance
+// from the image centre, inside-the-frame flag.  A cell's rectangles have their corners on it: the one the distance extrema are taken
+// over (the cell dilated by `dil` lattice steps) and the one that must map inside the frame before a lower bound is given (dilated by
+// `idil` steps: the support of the pyramid); off = max(dil, idil).  `slack`: source pixels added to the margin mg.px on both sides
+// (pyramid_slack) -- with it the extrema are those of the cell itself (dil 0) and only the inside test keeps the dilation.
 struct Lattice {
-    bool all = false; int nx = 0, ny = 0, dil = 1, cols = 0, rows = 0; double xc = 0, yc = 0, dis_max = 1, inv_dis_max = 1, M[9] = {};
+    bool all = false; int nx = 0, ny = 0, dil = 1, idil = 1, off = 1, cols = 0, rows = 0; double xc = 0, yc = 0, dis_max = 1, inv_dis_max = 1, M[9] = {};
+    double slack = 0;
     CullMargins mg;
     std::vector<double> sx, sy, d; std::vector<unsigned char> in;
     std::vector<double> pair_d; std::vector<unsigned char> pair_in; bool paired = false;      // raise_bounds' fast route
 
     // Points are mapped on first use (a shard asks for an eighth of them) unless map_all; one division per point, no square root.
-    void map_canvas(const double Minv[9], int crows, int ccols, int cols_, int rows_, int dil_, bool map_all, const CullMargins& m)
+    // in_dil < 0: the inside test over the same rectangle as the extrema (dil)
+    void map_canvas(const double Minv[9], int crows, int ccols, int cols_, int rows_, int dil_, bool map_all, const CullMargins& m, int in_dil = -1,
+                    double slack_ = 0.0)
     {
         all = map_all; mg = m; paired = false;
         dil = dil_;                                                 // dilation of a cell in lattice steps of 64 pixels
-        nx = ccols / 64 + 2 * dil + 1; ny = crows / 64 + 2 * dil + 1;
+        idil = in_dil < 0 ? dil_ : in_dil; off = std::max(dil, idil); slack = slack_;
+        nx = ccols / 64 + 2 * off + 1; ny = crows / 64 + 2 * off + 1;
         const size_t n = (size_t)nx * ny;
         sx.resize(n); sy.resize(n); d.resize(n); in.assign(n, 2);      // 2: not mapped yet
         xc = (double)(cols_ / 2); yc = (double)(rows_ / 2); dis_max = std::sqrt(xc * xc + yc * yc);
@@ -77,15 +110,15 @@ struct Lattice {
         for (int i = 0; i < 9; i++) M[i] = Minv[i];
         if (!map_all) return;                                       // a shard that owns a small part of the canvas asks for a fraction of the points: on first use
         // unsharded (or a shard that owns most of this canvas: the replicas of bench.py's weak mode own all of it), every point is needed (a cell's
-        // dilated rectangle has its corners on neighbouring points): all of them now, row by row,
+        // rectangles have their corners on neighbouring points): all of them now, row by row,
         // in loops without branches that the compiler turns into packed divisions (a third of the time of mapping them one by one)
         const double cmax = cols - 2.0, rmax = rows - 2.0;
         for (int m_ = 0; m_ < ny; m_++) {
-            const double y = 64.0 * (m_ - dil), n0 = M[1] * y + M[2], n1 = M[4] * y + M[5], w0 = M[7] * y + M[8];
+            const double y = 64.0 * (m_ - off), n0 = M[1] * y + M[2], n1 = M[4] * y + M[5], w0 = M[7] * y + M[8];
             double* __restrict__ psx = sx.data() + (size_t)m_ * nx; double* __restrict__ psy = sy.data() + (size_t)m_ * nx;
             double* __restrict__ pd = d.data() + (size_t)m_ * nx; unsigned char* __restrict__ pin = in.data() + (size_t)m_ * nx;
             for (int k = 0; k < nx; k++) {
-                const double x = 64.0 * (k - dil), iw = 1.0 / (M[6] * x + w0);
+                const double x = 64.0 * (k - off), iw = 1.0 / (M[6] * x + w0);
                 const double px = (M[0] * x + n0) * iw, py = (M[3] * x + n1) * iw, dx = px - xc, dy = py - yc;
                 psx[k] = px; psy[k] = py; pd[k] = dx * dx + dy * dy;
             }
@@ -97,7 +130,7 @@ struct Lattice {
     {
         const size_t o = (size_t)m * nx + k;
         if (in[o] == 2) {
-            const double x = 64.0 * (k - dil), y = 64.0 * (m - dil), iw = 1.0 / (M[6] * x + M[7] * y + M[8]);
+            const double x = 64.0 * (k - off), y = 64.0 * (m - off), iw = 1.0 / (M[6] * x + M[7] * y + M[8]);
             const double px = (M[0] * x + M[1] * y + M[2]) * iw, py = (M[3] * x + M[4] * y + M[5]) * iw;
             sx[o] = px; sy[o] = py;
             const double dx = px - xc, dy = py - yc;
@@ -108,8 +141,8 @@ struct Lattice {
     }
 
     // The radial weight (weightImage, MultiBandMap2DCPU.cpp:396-418, gathered at the NEAREST source pixel, 0 outside the frame) over the canvas
-    // rectangle with lattice corners (k, m) .. (k + span + 2 dil, m + span + 2 dil) -- a cell of a tile (span lattice steps on a side) dilated
-    // by 64 dil pixels -- against `wlb`, the lower bound of what the cell stores:
+    // rectangle 64 (k - dil, m - dil) .. 64 (k + span + dil, m + span + dil) -- the cell (k, m) of the canvas (span lattice steps on a side)
+    // dilated by 64 dil pixels -- against `wlb`, the lower bound of what the cell stores:
     //   returns true when every weight the keyframe can have there is below wlb (the cell is out);
     //   *wmin <= every weight it has there (0 unless the rectangle maps wholly inside the frame).
     // The rectangle maps to a convex quadrilateral Q of the source plane (M is projective and W keeps its sign, cull_frame_ok); the weight
@@ -117,19 +150,34 @@ struct Lattice {
     // farthest corner.  "Largest weight < wlb" <=> dist(c, Q) > T, T the distance at which the weight -- with the margins -- reaches
     // wlb; decided from the corners alone when one of them lies within T (most cells that stay in), by the exact point-to-quadrilateral
     // distance otherwise.
+    //
+    // With a slack (map_canvas) the weights bounded are those of EVERY pyramid level at the pixels whose level-0 position lies in the cell:
+    // such a weight is a convex combination of level-0 weights around that position, and differs from the radial weight AT the position by
+    // at most slack / dis_max (fusion_map.cpp, build_tile_table, has the argument).  The slack joins the pixel margin on both sides; the
+    // upper side bounds the combination through the Lipschitz function max(1 - d / dis_max, floor) >= weight, so a bound at or below
+    // floor + slack / dis_max culls nothing (floor: the weight image's own 1e-5, its square root for squared weights); the lower side
+    // needs every point of the combination inside the frame: the corners of the cell dilated by idil steps.
     bool cell_out(int k, int m, int span, int weight_type, float wlb, bool want_out, float* wmin)
     {
-        const int e = span + 2 * dil;                               // lattice steps across the dilated cell
-        const size_t c[4] = { point(k, m), point(k + e, m), point(k + e, m + e), point(k, m + e) };
+        const int e = span + 2 * dil, o = off - dil;                   // lattice steps across the dilated cell; its first corner
+        const size_t c[4] = { point(k + o, m + o), point(k + o + e, m + o), point(k + o + e, m + o + e), point(k + o, m + o + e) };
         const double d2[4] = { d[c[0]], d[c[1]], d[c[2]], d[c[3]] };
-        const double mpx = mg.px, mw = mg.w;
+        const double mpx = mg.px + slack, mw = mg.w;
         if (wmin) {                                                    // (nullptr: only the question whether the cell is out)
             *wmin = 0.f;
             // (weight type 0: wmin can exceed wlb only if the farthest corner lies within (1 - 1e-5 - wlb) dis_max - 2 of the centre -- in the steady
             // state it rarely does, and the square root is not taken)
             const double far2 = std::max(std::max(d2[0], d2[1]), std::max(d2[2], d2[3]));
             const double tw = weight_type == 0 ? (1.0 - mw - (double)wlb) * dis_max - mpx : 1e300;
-            if ((in[c[0]] & in[c[1]] & in[c[2]] & in[c[3]]) == 1 && tw > 0 && far2 < tw * tw * (1.0 + 1e-9)) {
+            bool inside = tw > 0 && far2 < tw * tw * (1.0 + 1e-9);
+            if (inside) {
+                if (idil == dil) inside = (in[c[0]] & in[c[1]] & in[c[2]] & in[c[3]]) == 1;
+                else {
+                    const int ei = span + 2 * idil, oi = off - idil;
+                    inside = (in[point(k + oi, m + oi)] & in[point(k + oi + ei, m + oi)] & in[point(k + oi + ei, m + oi + ei)] & in[point(k + oi, m + oi + ei)]) == 1;
+                }
+            }
+            if (inside) {
                 const double dfar = std::sqrt(far2) + mpx;
                 double w = 1.0 - dfar * inv_dis_max;
                 if (weight_type != 0) w = w > 0 ? w * w : 0.0;
@@ -141,6 +189,7 @@ struct Lattice {
         // T: weight(T - mpx) + mw == wlb
         double g = (double)wlb - mw;
         if (weight_type != 0) g = std::sqrt(g);
+        if (slack > 0 && !(g - slack * inv_dis_max > (weight_type != 0 ? 3.1623e-3 : 1e-5))) return false;      // within the slack of the weights' floor
         const double T = mpx + dis_max * (1.0 - g), T2 = T * T;
         if (d2[0] <= T2 || d2[1] <= T2 || d2[2] <= T2 || d2[3] <= T2) return false;      // a corner within T
         bool pos = true, neg = true; double dnear2 = 1e300;
@@ -175,24 +224,27 @@ struct Lattice {
         }
     }
     // Every lattice point is mapped (map_canvas), 4 x 4 cells: the same arithmetic as cell_out's first half, without its calls -- the farthest
-    // corner of a cell's dilated square from a pass (once per keyframe) that pairs the points e steps apart along a row first.  For host time.
+    // corner of a cell's dilated square from a pass (once per keyframe) that pairs the points e steps apart along a row first -- two pairings:
+    // the distances e = 1 + 2 dil apart, the inside flags ei = 1 + 2 idil apart.  For host time.
     void raise_bounds_fast(int x, int y, int weight_type, float wlb[16])
     {
-        const int e = 1 + 2 * dil;
+        const int e = 1 + 2 * dil, o = off - dil, ei = 1 + 2 * idil, oi = off - idil;
         if (!paired) {
             pair_d.resize((size_t)nx * ny); pair_in.resize((size_t)nx * ny);
             for (int m = 0; m < ny; m++) {
                 const double* __restrict__ dd = d.data() + (size_t)m * nx; const unsigned char* __restrict__ ii = in.data() + (size_t)m * nx;
                 double* __restrict__ pd = pair_d.data() + (size_t)m * nx; unsigned char* __restrict__ pi = pair_in.data() + (size_t)m * nx;
-                for (int k = 0; k + e < nx; k++) { pd[k] = std::max(dd[k], dd[k + e]); pi[k] = ii[k] & ii[k + e]; }
+                for (int k = 0; k + e < nx; k++) pd[k] = std::max(dd[k], dd[k + e]);
+                for (int k = 0; k + ei < nx; k++) pi[k] = ii[k] & ii[k + ei];
             }
             paired = true;
         }
-        const double mpx = mg.px, mw = mg.w;
+        const double mpx = mg.px + slack, mw = mg.w;
         for (int qy = 0; qy < 4; qy++) {
-            const size_t r0 = (size_t)(4 * y + qy) * nx + 4 * x, r1 = r0 + (size_t)e * nx;
+            const size_t r0 = (size_t)(4 * y + qy + o) * nx + 4 * x + o, r1 = r0 + (size_t)e * nx;
+            const size_t i0 = (size_t)(4 * y + qy + oi) * nx + 4 * x + oi, i1 = i0 + (size_t)ei * nx;
             for (int qx = 0; qx < 4; qx++) {
-                if (!(pair_in[r0 + qx] & pair_in[r1 + qx])) continue;              // not wholly inside the frame: wmin 0
+                if (!(pair_in[i0 + qx] & pair_in[i1 + qx])) continue;              // not wholly inside the frame: wmin 0
                 float& wl = wlb[4 * qy + qx];
                 const double far2 = std::max(pair_d[r0 + qx], pair_d[r1 + qx]);
                 const double tw = weight_type == 0 ? (1.0 - mw - (double)wl) * dis_max - mpx : 1e300;

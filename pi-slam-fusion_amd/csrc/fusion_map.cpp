@@ -215,7 +215,16 @@ bool FusionMap::render_frame(const QueuedFrame& f)
                 for (int x = 0; x < w.tx; x++) mine += tile_owner(opt_.shard_count, opt_.shard_block, w.xminInt + x + off_x_, w.yminInt + y + off_y_) == opt_.shard_rank;
             map_all = 4 * mine >= w.tx * w.ty;
         }
-        p.lat.map_canvas(w.Minv, w.crows, w.ccols, f.cols, f.rows, single_band_ ? 0 : ((2 << w.L) - 2 + 63) / 64, map_all, cull_margins_);
+        // multi-band: the bounds over the cell itself, widened by the pyramid's slack (build_tile_table has the argument); only the test
+        // that a lower bound's support lies inside the frame keeps the pyramid's reach, 2^(L+1) - 2 pixels rounded up to lattice steps.
+        // Experiments library, PF_CULL_DILATED=1: both bounds over the cell dilated by that reach and no slack (the rule before; A/B, tests)
+        static const bool dilated_rule = exp_env("PF_CULL_DILATED") != nullptr;
+        const int reach = single_band_ ? 0 : ((2 << w.L) - 2 + 63) / 64;
+        if (single_band_ || dilated_rule) p.lat.map_canvas(w.Minv, w.crows, w.ccols, f.cols, f.rows, reach, map_all, cull_margins_);
+        else {
+            const double far = 64.0 * reach, s = map_lipschitz(w.Minv, -far, w.ccols + far, -far, w.crows + far);
+            p.lat.map_canvas(w.Minv, w.crows, w.ccols, f.cols, f.rows, 0, map_all, cull_margins_, reach, pyramid_slack(s, w.L));
+        }
         if (lookahead_ok()) {
             // the keyframe's own lower bounds enter the tiles' wlb NOW: the keyframes ahead of it in the queue are decided against them
             if (!tiles_pool_.empty()) { p.tiles = std::move(tiles_pool_.back()); tiles_pool_.pop_back(); }
@@ -400,14 +409,24 @@ int FusionMap::frame_canvas(const QueuedFrame& f, FrameWork& w)
 // need rectangles shrink the grid to what the remaining cells depend on.  Nothing changes in what is stored: `if (srcW >= dstW)`
 // (.cpp:521, :542) is false at every pixel of such a cell.  Sound because both sides are bounded from the geometry alone, with margins
 // (cell_out):
-//   new weights   W_i(q) is a convex combination (pyrDown) of level-0 radial weights inside the cell dilated by the pyramid's
-//                 support radius 2^(L+1) px, so W_i <= wmax = the largest radial weight the frame can have there;
-//   stored ones   every earlier keyframe f whose canvas held the tile left S_i >= W_i^f >= wmin_f (its smallest weight on the same
-//                 dilated cell, 0 unless that lies wholly inside f's footprint) -- also when f itself was culled there, for
-//                 then S_i > W_i^f.  Tile::wlb[cell] = max over f of wmin_f.
+//   the weights   A pixel p of level i belongs to the cell that holds its level-0 position 2^i p.  Its weight W_i(p) is the level-0 weight
+//                 image v under the i-fold composition of pyrDown's [1 4 6 4 1] / 16: a convex combination of v centred on 2^i p with
+//                 variance (4^i - 1) / 3 per axis (BORDER_REFLECT_101 only folds positions towards the inside of the canvas), so
+//                 E |x - 2^i p| <= sqrt(2 (4^L - 1) / 3) =: rms (26 px for five bands, 104 for seven).  v(x) is a radial weight of the
+//                 source pixel H(x) -- Lipschitz in its distance from the image centre with constant 1 / dis_max -- or 0 outside the
+//                 frame, and H is Lipschitz on the canvas with constant s (map_lipschitz).  With S = s rms (pyramid_slack):
+//   new weights   W_i(p) <= max(radial weight at 2^i p, floor) + S / dis_max <= the weight at distance dist(centre, H(cell)) - S
+//                 (the zeros outside the frame only lower W; squared weights: E (w + t)^2 <= (w + S / dis_max)^2 as E t^2 <= (S / dis_max)^2);
+//   stored ones   every earlier keyframe f whose canvas held the tile left S_i >= W_i^f >= wmin_f = the weight at distance
+//                 (farthest corner of H_f(cell)) + S_f, provided every point of the combination maps inside f's frame -- the cell
+//                 dilated by the pyramid's support radius 2^(L+1) - 2 pixels, rounded up to lattice steps, does -- and 0 otherwise
+//                 (squared weights: Jensen); also when f itself was culled there, for then S_i > W_i^f.
+//                 Tile::wlb[cell] = max over f of wmin_f.
+// Only the support of the combination entered the rule before this one (both bounds over the dilated cell: 192 x 192 px for five bands;
+// experiments library, PF_CULL_DILATED=1); its concentration is what S uses.  Both are checked against the weights themselves on the host
+// (tests/cpp/cull_slack_check.cpp, frame_plan_check.cpp).
 // Bit-exactness is checked, not assumed: every parity test runs with the cull on; PF_CULL=0 turns it off.
-// The unit of the cull is a CELL of a tile (64 x 64 pixels, 16 per tile; experiments library, PF_CULL_SUB=2: a quadrant), dilated by the
-// pyramid's support radius 2^(L+1) - 2 pixels rounded up to the lattice step (62 -> 64 for five bands, 254 -> 256 for seven).  A tile whose
+// The unit of the cull is a CELL of a tile (64 x 64 pixels, 16 per tile; experiments library, PF_CULL_SUB=2: a quadrant).  A tile whose
 // cells are all out is left out of the launch; otherwise the cells that are out travel as flag bits of its table entry and the kernels do
 // not look at their pixels (kernels.hip, cell_culled), which may have been computed from input nobody produced.
 bool FusionMap::build_tile_table(const QueuedFrame& f, FrameWork& w)

@@ -2,9 +2,10 @@
 """Host-only model of the cull with a LOOKAHEAD window (no GPU, no library): how much of a keyframe's canvas still has to be rendered when the
 weight bounds of the next D keyframes are known before the keyframe is rendered.
 
-bench.py's cfg-A sortie, the cull's own rule per 64 x 64 cell of a tile dilated by 64 px (fusion_map.cpp, cell_out): a cell is out for keyframe k
-when the largest radial weight k can have on the dilated cell (+ margins) is below wlb = max over the keyframes admitted so far of the smallest
-weight each has there (0 unless the dilated cell maps wholly inside that keyframe).  D = 0 is the product of rounds 4-6.
+bench.py's cfg-A sortie, the cull's own rule per 64 x 64 cell of a tile (frame_plan.hpp, cell_out): a cell is out for keyframe k when the largest
+weight k can have there (+ margins) is below wlb = max over the keyframes admitted so far of the smallest weight each has there (0 unless the
+cell dilated by 64 px maps wholly inside that keyframe).  Two rules for "there": the cell dilated by 64 px (rounds 4-6), and the cell itself with
+the pyramid's slack added to the margin (the product's).  D = 0 is the product of rounds 4-6.
    fresh = "all"    a keyframe renders every cell of a tile nobody rendered before (rounds 4-6)
    fresh = "tile"   ... unless all 16 cells are out: the tile then stays fresh for the next keyframe
    fresh = "free"   cells of fresh tiles are culled like any other (needs tile slots whose weights start at 0)
@@ -54,22 +55,33 @@ class Frame:
         p = np.stack([gx - self.t[0], gy - self.t[1], np.full_like(gx, -self.t[2])], -1) @ self.R      # R^T (g - t)
         return CAM[2] * p[..., 0] / p[..., 2] + CAM[4], CAM[3] * p[..., 1] / p[..., 2] + CAM[5]
 
-    def bounds(self, ci0, cj0, ci1, cj1):
-        """ub, lb per cell of the cell range [ci0, ci1) x [cj0, cj1)"""
+    def bounds(self, ci0, cj0, ci1, cj1, slack=None):
+        """ub, lb per cell of the cell range [ci0, ci1) x [cj0, cj1).  slack None: both over the cell dilated by 64 px (the rule of rounds 4-6);
+        a number: both over the cell itself with `slack` source pixels added to the margin (frame_plan.hpp, pyramid_slack), the inside test
+        still over the dilated cell, and no bound below the weights' floor + slack"""
         i = np.arange(ci0, ci1)[None, :]; j = np.arange(cj0, cj1)[:, None]
-        xa, xb = (i - 1) * CELL, (i + 2) * CELL; ya, yb = (j - 1) * CELL, (j + 2) * CELL
-        xa, xb, ya, yb = [np.broadcast_to(a, (cj1 - cj0, ci1 - ci0)).astype(float) for a in (xa, xb, ya, yb)]
+        shape = (cj1 - cj0, ci1 - ci0)
+        dil = [np.broadcast_to(a, shape).astype(float) for a in ((i - 1) * CELL, (i + 2) * CELL, (j - 1) * CELL, (j + 2) * CELL)]
+        own = [np.broadcast_to(a, shape).astype(float) for a in (i * CELL, (i + 1) * CELL, j * CELL, (j + 1) * CELL)]
+        xa, xb, ya, yb = dil if slack is None else own
+        mpx = MPX + (slack or 0.0)
         far = np.zeros_like(xa); inside = np.ones_like(xa, bool)
         for gx, gy in ((xa, ya), (xb, ya), (xa, yb), (xb, yb)):
             u, v = self.image(gx, gy)
             far = np.maximum(far, np.hypot(u - CAM[4], v - CAM[5]))
+        da, db, dc, dd = dil
+        for gx, gy in ((da, dc), (db, dc), (da, dd), (db, dd)):
+            u, v = self.image(gx, gy)
             inside &= (u >= 1) & (u <= CAM[0] - 2) & (v >= 1) & (v <= CAM[1] - 2)
-        lb = np.where(inside, 1 - (far + MPX) / DMAX - MW, 0.0)
+        lb = np.where(inside, 1 - (far + mpx) / DMAX - MW, 0.0)
         lb = np.where(lb > 2e-5, lb, 0.0)
         nx, ny = np.clip(self.pc[0], xa, xb), np.clip(self.pc[1], ya, yb)
         u, v = self.image(nx, ny)
         near = np.hypot(u - CAM[4], v - CAM[5])
-        ub = 1 - np.maximum(near - MPX, 0) / DMAX + MW
+        if slack is None:
+            ub = 1 - np.maximum(near - MPX, 0) / DMAX + MW
+        else:
+            ub = np.maximum(1 - np.maximum(near - MPX, 0) / DMAX, 1e-5) + slack / DMAX + MW
         return ub, lb
 
 
@@ -84,7 +96,12 @@ def dilate(m, r):
     return o
 
 
-def run(n, D, fresh_mode, first=20):
+def pyramid_slack(s, L):
+    """source pixels: the map's Lipschitz constant times the RMS spread of L pyrDown steps (frame_plan.hpp)"""
+    return s * math.sqrt(2.0 * (4.0 ** L - 1.0) / 3.0)
+
+
+def run(n, D, fresh_mode, first=20, slack=None):
     poses = wl.serpentine(CAM, H, n, max_rows=16)
     frames = [Frame(p) for p in poses]
     ox = min(f.x0 for f in frames) - 20; oy = min(f.y0 for f in frames) - 20
@@ -96,7 +113,7 @@ def run(n, D, fresh_mode, first=20):
         ti1, tj1 = int(math.ceil((f.x1 - ox) / (4 * CELL))), int(math.ceil((f.y1 - oy) / (4 * CELL)))
         rng.append((ti0, tj0, ti1, tj1))
         g = Frame.__new__(Frame); g.__dict__ = dict(f.__dict__); g.t = f.t - np.array([ox, oy, 0]); g.pc = f.pc - np.array([ox, oy])
-        B.append(g.bounds(4 * ti0, 4 * tj0, 4 * ti1, 4 * tj1))
+        B.append(g.bounds(4 * ti0, 4 * tj0, 4 * ti1, 4 * tj1, slack))
     admitted = 0
     tot = rend = run1 = run2 = 0
     for k in range(n):
@@ -125,8 +142,11 @@ def run(n, D, fresh_mode, first=20):
 
 if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 220
-    print("| lookahead D | fresh tiles | rendered share | within 1 cell | within 2 cells |\n|---|---|---|---|---|")
+    # both rules: the dilated cell, and the cell itself with the slack of five bands on the sortie's nearly nadir maps (s = 1.05)
+    S = pyramid_slack(1.05, 5)
+    print("| lookahead D | fresh tiles | rule | rendered share | within 1 cell | within 2 cells |\n|---|---|---|---|---|---|")
     for mode in ("all", "tile", "free"):
         for D in (0, 1, 2, 4, 8, 20, 40):
-            a, b, c = run(n, D, mode)
-            print("| %d | %s | %.3f | %.3f | %.3f |" % (D, mode, a, b, c), flush=True)
+            for rule, slack in (("dilated", None), ("slack %.1f px" % S, S)):
+                a, b, c = run(n, D, mode, slack=slack)
+                print("| %d | %s | %s | %.3f | %.3f | %.3f |" % (D, mode, rule, a, b, c), flush=True)
