@@ -42,12 +42,12 @@ def slot_layout(bands, force_float):
     return {"nlev": nlev, "lap_off": lap_off, "w_off": w_off, "total": off}
 
 
-def pack(lap, w):
-    """[lap_0 .. lap_L] (s x s x 3, int16 or float32) and [w_0 .. w_L] (s x s float32) -> the slot's bytes, padding = 0xA5"""
+def pack(lap, w, pad=PAD):
+    """[lap_0 .. lap_L] (s x s x 3, int16 or float32) and [w_0 .. w_L] (s x s float32) -> the slot's bytes, padding = pad (0xA5)"""
     ff = lap[0].dtype == np.float32
     lay = slot_layout(len(lap) - 1, ff)
     assert len(lap) == len(w) == lay["nlev"]
-    out = np.full(lay["total"], PAD, np.uint8)
+    out = np.full(lay["total"], pad, np.uint8)
     for i in range(lay["nlev"]):
         s = ELE >> i
         assert lap[i].shape == (s, s, 3) and lap[i].dtype == (np.float32 if ff else np.int16) and w[i].shape == (s, s) and w[i].dtype == np.float32

@@ -37,10 +37,26 @@ def header(**over):
     return b
 
 
-def record(ix, iy, nbytes, seed=0, wlb=None):
+def record(ix, iy, nbytes, seed=0, wlb=None, image=None):
+    """one tile record; image: the slot image (nbytes of uint8, e.g. pyramid_inject.pack's), None: random bytes of `seed`"""
     w = np.full(16, -1.0, np.float32) if wlb is None else np.asarray(wlb, np.float32)
-    body = np.random.RandomState(seed).randint(0, 256, nbytes).astype(np.uint8).tobytes()
+    if image is None:
+        body = np.random.RandomState(seed).randint(0, 256, nbytes).astype(np.uint8).tobytes()
+    else:
+        body = np.ascontiguousarray(image, np.uint8).tobytes()
+        assert len(body) == nbytes
     return struct.pack("<2i", ix, iy) + w.tobytes() + body
+
+
+def with_tile_count(head, n):
+    """a header (the first 256 bytes of a real map's file) with n_tiles = n: the header of a file of n records"""
+    assert len(head) == HEADER_BYTES and head[:8] == MAGIC
+    return head[:40] + struct.pack("<Q", n) + head[48:]
+
+
+def grid_of(head):
+    """(w, h, off_x, off_y) of a header: the tile coordinates its records may carry"""
+    return struct.unpack("<4i", head[HEADER_BYTES - 16:HEADER_BYTES])
 
 
 def state_file(tiles=((-1, 0), (1, 1)), wlbs=None, **over):
