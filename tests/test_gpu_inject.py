@@ -217,9 +217,9 @@ def test_a_keyframe_over_imported_tiles_equals_the_model(pf, orc, ff):
     tile keyframe 1 covers -- weights half zero in one, a constant 1e30 in another, all zero or half zero in the rest -- and keyframe 1
     is fed: the import leaves "nothing known" bounds, so no cell may be skipped on the strength of keyframe 0's.  Every level of
     every tile equals the model's select over the imported arrays.
-    What this does not do yet: with these poses no cell of keyframe 1 lies wholly under keyframe 0's bounds, so a library whose
-    tile_import kept the old bounds passes as well (tried once, on a scratch build).  The select over imported weights -- zeros, a
-    weight nothing beats, `>=` at every level -- is what is pinned."""
+    The select over imported weights -- zeros, a weight nothing beats, `>=` at every level -- is what is pinned here.  With these
+    poses no cell of keyframe 1 lies wholly under keyframe 0's bounds: that tile_import forgets the old bounds is pinned by
+    tests/test_gpu_feed_slots.py::test_import_forgets_the_cull_bounds, on a rig where the cull bites."""
     from helpers import feed_with_model, hostile_frame, workloads
     from map_model import ModelMap
     from test_gpu_model import CAM, COLS, MIXED, ROWS, lattice_poses
