@@ -277,6 +277,49 @@ int     pf_tiff_write_device_lossless(const char* filename, const void* dev_bgr,
  * where the collapse left it, under the one hold of the map; single-band maps take the host writer.  pf_save("x.tif") and
  * pf_save_tiff keep writing JPEG tiles. */
 int     pf_save_tiff_lossless(pf_map* m, const char* filename, int masked, int force_bigtiff);
+/* The PNG of save_png (csrc/png_encode.hpp, the format's one definition): an image of rows x cols BGR pixels (`step` bytes per row,
+ * 0 = packed) and, optionally, a mask (a byte per pixel, `mask_step` bytes per row, 0 = packed) as one complete PNG file that any
+ * reader takes.
+ *   file     signature | IHDR: 8 bits, colour type 2 (RGB), or 6 (RGBA) when a mask is given, compression 0, filter method 0, no
+ *            interlace | IDAT chunks | IEND.  No other chunks.
+ *   F        the filtered stream: for every row the filter-type byte 1 (Sub), then the samples in R, G, B (, A) order, each minus
+ *            the same channel of the pixel to its left, mod 256; the row's first pixel as it is.  A = 255 where the mask byte is not
+ *            0, else 0; the colour under A = 0 is the image's.  N = rows * (1 + cols * bpp) bytes, bpp 3 or 4.
+ *   blocks   F is cut into deflate blocks of 12 288 stream bytes, row ends ignored; the last is shorter.  Tokens, codes and the
+ *            length builder are those of pf_deflate_tile_bgr above, history carrying across blocks (the run that begins a block
+ *            which is not the stream's first takes no literal when the byte before the block has its value).  A block is dynamic
+ *            when its bits are no more than those of storing it at the bit it begins at -- 3 bits, zero bits up to a byte, LEN,
+ *            NLEN, its own bytes -- else it is stored.  Only the stream's last block has BFINAL.
+ *   segments sixteen blocks, joined bit by bit.  Every segment but the last ends with an empty stored block (BFINAL 0: three zero
+ *            bits, zero bits up to a byte, 00 00 FF FF), so every segment begins on a byte.
+ *   chunks   one segment is one IDAT chunk.  The first begins with the zlib header 78 01, the last ends with zero bits up to a byte
+ *            and the Adler-32 of F, big-endian.  Chunk CRCs: CRC-32, polynomial 0xEDB88320 reflected, over type and data.
+ *   bound    no file is longer than N + 5 per block + (5 + 12) per segment + 51 bytes.  Offsets and lengths that address the stream or
+ *            the file are 64-bit; refused before anything is written: a row of F past 2^31 - 1 bytes, more than 2^31 - 1 blocks.
+ * pf_png_encode_bgr: host code, no device.  out = NULL: *len = the bound.  Otherwise *len = the file's length, and the file is in
+ * `out` if it fits `cap` (0 + pf_last_error() if not; nothing is written then).  0 also for no image, sizes that are not positive and
+ * a step smaller than a row (*len = 0 then).
+ * pf_png_encode_device: the same file, byte for byte, from an image (and a mask, or NULL) in device memory, made on the GPU
+ * (csrc/png_encode.hip), chunk CRCs and the Adler-32 included; the passes run in the order of hip_stream and the call returns when the
+ * file is in `out`.  The same conventions.
+ * The checksum functions are the format's own (csrc/png_encode.hpp), host code: pf_png_crc32 continues crc (0 at the start) over
+ * data; pf_png_crc32_combine gives the CRC of A || B from those of A and B and the length of B (crc_a times x^(8 len_b) mod P, plus
+ * crc_b); pf_png_adler32 is built block by block from the sums S = sum x_k and T = sum (n - k) x_k the kernels make;
+ * pf_png_adler32_combine gives the Adler-32 of A || B likewise. */
+int      pf_png_encode_bgr(const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,
+                           uint8_t* out, size_t cap, size_t* len);
+int      pf_png_encode_device(const void* dev_bgr, int rows, int cols, size_t step, const void* dev_mask, size_t mask_step,
+                              uint8_t* out, size_t cap, size_t* len, void* hip_stream);
+uint32_t pf_png_crc32(uint32_t crc, const uint8_t* data, size_t len);
+uint32_t pf_png_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+uint32_t pf_png_adler32(const uint8_t* data, size_t len);
+uint32_t pf_png_adler32_combine(uint32_t adler_a, uint32_t adler_b, uint64_t len_b);
+/* A map's mosaic as that file, under any name: pf_png_encode_bgr of the pixels pf_save_to_memory returns, or, masked != 0, of the
+ * pixels and the mask pf_save_to_memory_mask returns -- an RGBA file whose alpha is 0 exactly where pf_save paints the background.
+ * Multi-band maps encode on the GPU from the mosaic (and the coverage) where the collapse left them, under the one hold of the map;
+ * the complete file crosses to the host once.  Single-band maps take the host encoder, covered meaning the tile's alpha byte is not
+ * 0.  A map without content returns 0.  pf_save("x.png") keeps its route and its bytes. */
+int      pf_save_png(pf_map* m, const char* filename, int masked);
 /* cv::imencode(".jpg") / the JPEG leg of cv::imwrite of OpenCV 2.4.9: baseline JPEG, byte for byte what libjpeg writes after
  * jpeg_set_defaults, JCS_RGB input and jpeg_set_quality(quality, TRUE) -- JFIF 1.01, 4:2:0, the Annex K tables, one interleaved
  * scan, integer colour conversion and ISLOW DCT.  bgr: rows x cols 8-bit BGR, `step` bytes per row (0 = packed).  quality is

@@ -176,6 +176,8 @@ public:
     bool save(const std::string& filename) { return pf_save(h_, filename.c_str()) != 0; }
     // the mosaic as a tiled pyramid TIFF with lossless (Deflate, Predictor 2) tiles, under any name (pf_save_tiff_lossless)
     bool saveLossless(const std::string& filename, bool masked = false, bool force_bigtiff = false) { return pf_save_tiff_lossless(h_, filename.c_str(), masked, force_bigtiff) != 0; }
+    // the mosaic as a PNG encoded on the GPU, under any name; masked: RGBA, transparent where save() paints the background (pf_save_png)
+    bool savePng(const std::string& filename, bool masked = false) { return pf_save_png(h_, filename.c_str(), masked ? 1 : 0) != 0; }
     bool saveTiff(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }
     // the pyramid TIFF with a transparency mask behind every image: covered where the level-0 weight is not 0 (pf_save_tiff_masked)
     bool saveMasked(const std::string& filename, int quality = 95, bool force_bigtiff = false) { return pf_save_tiff_masked(h_, filename.c_str(), quality, force_bigtiff ? 1 : 0) != 0; }

@@ -152,6 +152,14 @@ def lib():
         L.pf_tiff_write_device_lossless.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, dp, C.c_int, vp]
         L.pf_save_tiff_lossless.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
         L.pf_debug_tiff_counts.argtypes = [vp, C.POINTER(C.c_longlong)]; L.pf_debug_tiff_counts.restype = None
+    if hasattr(L, "pf_png_encode_bgr") or not os.environ.get("PF_LIB"):
+        L.pf_png_encode_bgr.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.pf_png_encode_device.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+        L.pf_png_crc32.argtypes = [C.c_uint32, vp, C.c_size_t]; L.pf_png_crc32.restype = C.c_uint32
+        L.pf_png_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]; L.pf_png_crc32_combine.restype = C.c_uint32
+        L.pf_png_adler32.argtypes = [vp, C.c_size_t]; L.pf_png_adler32.restype = C.c_uint32
+        L.pf_png_adler32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]; L.pf_png_adler32_combine.restype = C.c_uint32
+        L.pf_save_png.argtypes = [vp, C.c_char_p, C.c_int]
     if hasattr(L, "pf_webtiles") or not os.environ.get("PF_LIB"):
         L.pf_webtiles_georef.argtypes = [vp, dp, dp, ip, ip]
         L.pf_webtiles_georef_compose.argtypes = [dp, dp, dp, dp]
@@ -526,6 +534,49 @@ def tiff_write_device_lossless(filename, dev_ptr, rows, cols, dev_mask=None, bg=
     """The same file, byte for byte, from pixels (and a byte-per-pixel mask, or None) at device addresses (csrc/overview.hip + deflate_encode.hip)."""
     keep, xf = _transform16(model_transform)
     return bool(lib().pf_tiff_write_device_lossless(filename.encode(), dev_ptr, rows, cols, step, dev_mask, mask_step, bg, xf, int(force_bigtiff), stream))
+
+
+def _png_mask(mask, shape, who):
+    if mask is None:
+        return None, None, 0
+    m = np.asarray(mask)
+    if m.dtype == np.bool_:
+        m = m.astype(np.uint8)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+    if m.shape != shape:
+        raise ValueError("%s: HxWx3 and HxW expected" % who)
+    return m, m.ctypes.data, m.strides[0]
+
+
+def png_encode(bgr, mask=None):
+    """HxWx3 BGR uint8 (rows may be padded) and, optionally, an HxW mask (non-zero = covered) -> the bytes of the PNG file of
+    pf_png_encode_bgr (include/pifusion.h): RGB, or RGBA with alpha 255 where covered; Sub filter, run-length deflate.  Host code."""
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(bgr, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("png_encode: HxWx3 expected")
+    keep, mp, ms = _png_mask(mask, a.shape[:2], "png_encode")
+    L = lib(); n = C.c_size_t(0)
+    if not L.pf_png_encode_bgr(a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], mp, ms, None, 0, C.byref(n)):
+        raise ValueError("png_encode: %s" % L.pf_last_error().decode())
+    out = np.empty(n.value, np.uint8)
+    if not L.pf_png_encode_bgr(a.ctypes.data, a.shape[0], a.shape[1], a.strides[0], mp, ms, out.ctypes.data, out.size, C.byref(n)):
+        raise ValueError("png_encode: %s" % L.pf_last_error().decode())
+    return out[:n.value].tobytes()
+
+
+def png_encode_device(dev_ptr, rows, cols, dev_mask=None, step=0, mask_step=0, stream=None):
+    """The same file, byte for byte, made on the GPU (csrc/png_encode.hip) from rows x cols BGR8 pixels at the device address `dev_ptr`
+    (`step` bytes per row, 0 = packed) and a byte-per-pixel mask at `dev_mask` (or None), its passes in the order of `stream`."""
+    L = lib(); n = C.c_size_t(0)
+    if not L.pf_png_encode_device(dev_ptr, rows, cols, step, dev_mask, mask_step, None, 0, C.byref(n), stream):
+        raise ValueError("png_encode_device: %s" % L.pf_last_error().decode())
+    out = np.empty(n.value, np.uint8)
+    if not L.pf_png_encode_device(dev_ptr, rows, cols, step, dev_mask, mask_step, out.ctypes.data, out.size, C.byref(n), stream):
+        raise ValueError("png_encode_device: %s" % L.pf_last_error().decode())
+    return out[:n.value].tobytes()
 
 
 def tiff_counts(map2d=None):
@@ -939,6 +990,10 @@ class Map2D:
     def save_tiff_lossless(self, filename, masked=False, force_bigtiff=False):
         """the mosaic as a pyramid TIFF with lossless (Deflate) tiles, with or without the transparency masks (pf_save_tiff_lossless)"""
         return bool(lib().pf_save_tiff_lossless(self._h, filename.encode(), int(masked), int(force_bigtiff)))
+
+    def save_png(self, filename, masked=False):
+        """the mosaic as a PNG encoded on the GPU, under any name (pf_save_png); masked: RGBA, alpha 0 where save() paints the background"""
+        return bool(lib().pf_save_png(self._h, filename.encode(), int(masked)))
 
     def save_to_memory_mask(self):
         """(mosaic BGR8, coverage HxW uint8: 255 where the level-0 weight is not 0, (tile x0, tile y0)) of one moment"""

@@ -114,6 +114,7 @@ int pf_sync(pf_map* m) { return m && m->impl.sync(); }
 int pf_save(pf_map* m, const char* filename) { return m && filename && m->impl.save(filename); }
 int pf_save_tiff(pf_map* m, const char* filename, int quality, int force_bigtiff) { return m && filename && m->impl.save_tiff(filename, quality, force_bigtiff != 0); }
 int pf_save_tiff_lossless(pf_map* m, const char* filename, int masked, int force_bigtiff) { return m && filename && m->impl.save_tiff_lossless(filename, masked != 0, force_bigtiff != 0); }
+int pf_save_png(pf_map* m, const char* filename, int masked) { return m && filename && m->impl.save_png(filename, masked != 0); }
 int pf_save_tiff_masked(pf_map* m, const char* filename, int quality, int force_bigtiff) { return m && filename && m->impl.save_tiff_masked(filename, quality, force_bigtiff != 0); }
 // pf_write_image / pf_image_info / pf_read_image: image_io.cpp (host code without a HIP dependency: also built by the sanitizer targets)
 int pf_jpeg_info(const uint8_t* data, size_t len, int* rows, int* cols, int* components) { return pf::jpeg_info(data, len, rows, cols, components); }
@@ -262,6 +263,40 @@ int pf_tiff_write_device_lossless(const char* filename, const void* dev_bgr, int
     mk.dev_bytes = dev_mask; mk.step = mask_step;
     const int ok = shared_tiff_device(at.device)->write(filename, dev_bgr, rows, cols, step, 0, bg, model_transform, force_bigtiff != 0, *shared_jpeg_encoder(at.device), hip_stream,
                                                         dev_mask ? &mk : nullptr, shared_deflate_encoder(at.device));
+    if (at.device != prev) (void)hipSetDevice(prev);
+    return ok;
+}
+// pf_png_encode_device's encoder: one per device, as the JPEG one
+static pf::PngEncoder* shared_png_encoder(int device)
+{
+    static pf::PngEncoder* e[64] = {};
+    if (device < 0 || device >= 64) device = 0;
+    if (!e[device]) e[device] = new pf::PngEncoder();
+    return e[device];
+}
+int pf_png_encode_device(const void* dev_bgr, int rows, int cols, size_t step, const void* dev_mask, size_t mask_step, uint8_t* out, size_t cap, size_t* len, void* hip_stream)
+{
+    std::lock_guard<std::mutex> l(g_jpeg_mu);
+    if (!len) { pf::set_error("pf_png_encode_device: no length"); return 0; }
+    *len = 0;
+    if (!pf::png_args_ok("pf_png_encode_device", dev_bgr, rows, cols, step, dev_mask, mask_step)) return 0;
+    pf::png::Geometry g;
+    (void)pf::png::geometry(rows, cols, dev_mask != nullptr, g);
+    if (!out) { *len = (size_t)g.bound; return 1; }
+    hipPointerAttribute_t at{}, am{};
+    if (hipPointerGetAttributes(&at, dev_bgr) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); pf::set_error("pf_png_encode_device: the image is not in device memory"); return 0; }
+    if (dev_mask && (hipPointerGetAttributes(&am, dev_mask) != hipSuccess || am.type != hipMemoryTypeDevice || am.device != at.device)) {
+        (void)hipGetLastError(); pf::set_error("pf_png_encode_device: the mask is not in device memory beside the image"); return 0;
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (at.device != prev && hipSetDevice(at.device) != hipSuccess) { pf::set_error("pf_png_encode_device: hipSetDevice failed"); return 0; }
+    pf::PngEncoder* e = shared_png_encoder(at.device);
+    int ok = e->encode(dev_bgr, rows, cols, step, dev_mask, mask_step, len, hip_stream);
+    if (ok) {
+        if (*len > cap) { pf::set_error("pf_png_encode_device: the file has " + std::to_string(*len) + " bytes, the buffer " + std::to_string(cap)); ok = 0; }
+        else ok = e->fetch(out, hip_stream);
+    }
     if (at.device != prev) (void)hipSetDevice(prev);
     return ok;
 }

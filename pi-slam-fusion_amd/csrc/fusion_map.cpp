@@ -75,7 +75,7 @@ FusionMap::~FusionMap()
     }
     for (auto e : merge_ev_) if (e) (void)hipEventDestroy(e);
     for (auto e : view_ev_) if (e) (void)hipEventDestroy(e);
-    jpeg_enc_.release(); deflate_enc_.release(); tiff_dev_.release();
+    jpeg_enc_.release(); deflate_enc_.release(); png_enc_.release(); tiff_dev_.release();
     (void)hipStreamDestroy(stream_);
     // the buffers (DevBuf), the tile store, the output ring and the profiler free what they hold as the members go, after this body: on
     // this thread, with the device current and nothing in flight.  None of them uses stream_

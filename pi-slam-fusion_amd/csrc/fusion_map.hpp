@@ -11,6 +11,7 @@
 #include "image_io.hpp"
 #include "jpeg_encode.hpp"
 #include "tiff_pyramid.hpp"
+#include "png_encode.hpp"
 #include "webtiles.hpp"
 #include "merge.hpp"
 #include "undistort.hpp"
@@ -80,6 +81,8 @@ public:
     bool save_tiff_masked(const char* filename, int quality, bool force_bigtiff) { return save_file(filename, tiff_route(single_band_), quality, force_bigtiff, nullptr, true); }
     // the lossless file (pf_save_tiff_lossless): a TIFF under any name with Deflate tiles, masked or not
     bool save_tiff_lossless(const char* filename, bool masked, bool force_bigtiff) { return save_file(filename, tiff_lossless_route(single_band_), 0, force_bigtiff, nullptr, masked); }
+    // the mosaic as the PNG of pf_png_encode_bgr under any name (pf_save_png): RGB, or, masked, RGBA with alpha 0 where save() paints the background
+    bool save_png(const char* filename, bool masked) { return save_file(filename, png_route(single_band_), 0, false, nullptr, masked); }
     // pf_debug_tiff_counts: tiles, empty tiles and device bytes of the last TIFF this map made on the GPU
     void tiff_counts(size_t* tiles, size_t* empty, size_t* device_bytes) { std::lock_guard<std::mutex> l(mu_); tiff_dev_.last_counts(tiles, empty, device_bytes); }
     // pf_webtiles: what the tiles are made for and where they go
@@ -432,6 +435,7 @@ private:
     DevBuf cover_plane_, cover_bytes_;          // pf_save_to_memory_mask: the mosaic's coverage as a bit plane (coverage.hip), and as bytes
     TiffDevice  tiff_dev_;      // save("x.tif"): level buffers and flags of its own, tiles through jpeg_enc_
     DeflateEncoder deflate_enc_;   // save_tiff_lossless(): the tiles of tiff_dev_'s levels on stream_, buffers of its own
+    PngEncoder  png_enc_;       // save_png(): reads blend_out_bgr_ (and cover_bytes_) on stream_, buffers of its own
     JpegEncoder jpeg_enc_;      // save("x.jpg"), pf_blend_tiles_jpeg: reads blend_out_bgr_ on stream_, buffers of its own
     OutRing     out_ring_;      // results on their way to the host
     bool export_webtiles(const SaveTarget& t, const WebTilesJob& job);                        // blend_out_bgr_ + cover_bytes_ of extent t -> the job's map tiles

@@ -8,6 +8,7 @@
 #include "jpeg_decode.hpp"
 #include "jpeg_encode.hpp"
 #include "tiff_pyramid.hpp"
+#include "png_encode.hpp"
 #include "raw_convert.hpp"
 #include <algorithm>
 #include <atomic>
@@ -173,6 +174,28 @@ bool write_tiff_lossless_file(const char* who, const char* filename, const uint8
     catch (const std::bad_alloc&) { std::remove(filename); set_error(std::string(who) + ": out of memory"); return false; }
 }
 
+// what both PNG encoders refuse, with the reason; step and mask_step come back with 0 resolved
+bool png_args_ok(const char* who, const void* bgr, int rows, int cols, size_t& step, const void* mask, size_t& mask_step)
+{
+    if (!bgr || rows <= 0 || cols <= 0) { set_error(std::string(who) + ": no image or a size that is not positive"); return false; }
+    png::Geometry g;
+    if (!png::geometry(rows, cols, mask != nullptr, g)) { set_error(std::string(who) + ": the image has " + std::to_string(cols) + " x " + std::to_string(rows) + " pixels, more than the encoder indexes"); return false; }
+    if (step == 0) step = (size_t)cols * 3;
+    if (mask_step == 0) mask_step = (size_t)cols;
+    if (step < (size_t)cols * 3 || (mask && mask_step < (size_t)cols)) { set_error(std::string(who) + ": step is smaller than a row"); return false; }
+    return true;
+}
+
+bool write_png_file(const char* who, const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step)
+{
+    if (!filename) { set_error(std::string(who) + ": no name"); return false; }
+    if (!png_args_ok(who, bgr, rows, cols, step, mask, mask_step)) return false;
+    std::vector<uint8_t> file;
+    try { if (!png::encode(bgr, rows, cols, step, mask, mask_step, file)) return false; } catch (const std::bad_alloc&) { set_error(std::string(who) + ": out of memory"); return false; }
+    if (!write_bytes_file(filename, file.data(), file.size())) { std::remove(filename); return false; }
+    return true;
+}
+
 bool jpeg_size_ok(const char* who, int rows, int cols)
 {
     if (rows <= jenc::kMaxDim && cols <= jenc::kMaxDim) return true;
@@ -238,6 +261,25 @@ int pf_jpeg_encode_bgr(const uint8_t* bgr, int rows, int cols, size_t step, int 
     std::memcpy(out, stream.data(), stream.size());
     return 1;
 }
+int pf_png_encode_bgr(const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step, uint8_t* out, size_t cap, size_t* len)
+{
+    if (!len) { pf::set_error("pf_png_encode_bgr: no length"); return 0; }
+    *len = 0;
+    if (!pf::png_args_ok("pf_png_encode_bgr", bgr, rows, cols, step, mask, mask_step)) return 0;
+    pf::png::Geometry g;
+    (void)pf::png::geometry(rows, cols, mask != nullptr, g);
+    if (!out) { *len = (size_t)g.bound; return 1; }
+    std::vector<uint8_t> file;
+    try { (void)pf::png::encode(bgr, rows, cols, step, mask, mask_step, file); } catch (const std::bad_alloc&) { pf::set_error("pf_png_encode_bgr: out of memory"); return 0; }
+    *len = file.size();
+    if (file.size() > cap) { pf::set_error("pf_png_encode_bgr: the file has " + std::to_string(file.size()) + " bytes, the buffer " + std::to_string(cap)); return 0; }
+    std::memcpy(out, file.data(), file.size());
+    return 1;
+}
+uint32_t pf_png_crc32(uint32_t crc, const uint8_t* data, size_t len) { return data || !len ? pf::png::crc32(crc, data, len) : crc; }
+uint32_t pf_png_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return pf::png::crc_combine(crc_a, crc_b, len_b); }
+uint32_t pf_png_adler32(const uint8_t* data, size_t len) { return data || !len ? pf::png::adler32(data, len) : 1; }
+uint32_t pf_png_adler32_combine(uint32_t adler_a, uint32_t adler_b, uint64_t len_b) { return pf::png::adler_combine(adler_a, adler_b, len_b); }
 int pf_tiff_write_bgr(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, int quality, int bg, const double model_transform[16], int force_bigtiff)
 { return pf::write_tiff_file("pf_tiff_write_bgr", filename, bgr, rows, cols, step, quality, bg, model_transform, force_bigtiff != 0); }
 int pf_tiff_write_bgr_masked(const char* filename, const uint8_t* bgr, int rows, int cols, size_t step, const uint8_t* mask, size_t mask_step,

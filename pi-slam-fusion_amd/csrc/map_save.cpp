@@ -130,6 +130,16 @@ bool FusionMap::save_mosaic(SaveTarget& t, const std::vector<ForeignTile>* forei
         return tiff_dev_.write(t.name, blend_out_bgr_.p, t.rows, t.cols, (size_t)t.cols * 3, t.quality, opt_.bg_color, t.transform, t.force_bigtiff, jpeg_enc_, stream_,
                                t.masked ? &mk : nullptr, t.route == SaveRoute::DeviceTiffLossless ? &deflate_enc_ : nullptr);
     }
+    if (t.route == SaveRoute::DevicePng) {          // the whole file is made in HBM and crosses once
+        if (t.masked && !coverage()) return false;
+        size_t step = 0, mask_step = 0, len = 0;
+        if (!png_args_ok("save_png", blend_out_bgr_.p, t.rows, t.cols, step, t.masked ? cover_bytes_.p : nullptr, mask_step)) return false;          // before anything is made: no file
+        if (!png_enc_.encode(blend_out_bgr_.p, t.rows, t.cols, step, t.masked ? cover_bytes_.p : nullptr, mask_step, &len, stream_)) return false;
+        const uint8_t* file_bytes = png_enc_.fetch_pinned(stream_);
+        if (!file_bytes) return false;
+        if (!write_bytes_file(t.name, file_bytes, len)) { std::remove(t.name); return false; }
+        return true;
+    }
     size_t off[2];                                 // cv::imwrite's JPEG defaults: quality 95, 4:2:0
     if (!jpeg_enc_.encode(blend_out_bgr_.p, 1, nullptr, 0, t.rows, t.cols, (size_t)t.cols * 3, t.quality, off, stream_)) return false;
     const uint8_t* stream = jpeg_enc_.fetch_pinned(stream_);
@@ -220,6 +230,7 @@ bool FusionMap::save_file(const char* filename, SaveRoute route, int quality, bo
     }
     if (route == SaveRoute::HostTiffLossless &&
         !write_tiff_lossless_file("save", filename, img.data(), t.rows, t.cols, 0, masked ? cover.data() : nullptr, 0, opt_.bg_color, t.transform, force_bigtiff)) return false;
+    if (route == SaveRoute::HostPng && !write_png_file("save_png", filename, img.data(), t.rows, t.cols, 0, masked ? cover.data() : nullptr, 0)) return false;
     if (route == SaveRoute::HostImage && !write_image_file(filename, img.data(), t.rows, t.cols)) return false;
     std::printf("Resolution:[%d %d]\n", t.cols, t.rows);
     return true;
